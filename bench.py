@@ -32,6 +32,15 @@ rung that ran (`config.memory_ladder`, `capacity_ring_slices`, `config.workload`
 Prints ONE JSON line on rank 0.  `value` = lattice-site iterations per second summed over all
 GPUs (iterations/s x global volume) with all inputs resident in HBM; iterations/s and the achieved
 algorithmic HBM GB/s are reported next to it.
+
+A plain run sets up, warms up, times exactly --steps iterations and prints the line.  `--full` adds what the headline does
+not need: per-kernel times from HIP events in the timed region (`kernel_ms`, `roofline`, the bytes moved, the PMC traffic
+where profiles/hbm_traffic.json holds the shape, `comm_ms_per_iteration`) and, on one GPU, the CPU baseline (unless
+--no-cpu-baseline).  `--dump-outputs DIR` writes, after the timed steps, a fixed sample of what the timed solve leaves a
+caller (the solutions X_s at seeded sites, and the residual) as DIR/<name>.npy in float64, at most 64 MB in all; the inputs
+are seeded, so two builds run with the same arguments can be compared output for output.  The half-volume form (--half, or
+the memory ladder's last rung, which the default multi-GPU shape can step down to on its own) runs two solves and names
+their files even_* and odd_*: two runs that land on different rungs did different work and dump different files.
 """
 import argparse
 import json
@@ -49,6 +58,42 @@ HBM_PEAK_GBPS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: 8.0 TB/s spec 
 FP64_PEAK_TFLOPS = 78.6
 SHIFTS = [0.0, 1e-6, 1e-4, 1e-2, 1e-5, 1e-3, 1e-1, 1.0]  # SURVEY.md section 8d; first S, sorted
 MASS = 1e-3
+DUMP_SITES = 2048  # --dump-outputs: sites sampled per solve over all ranks, fewer where that would pass DUMP_LIMIT
+DUMP_SEED = 7
+DUMP_LIMIT = 64 * 2 ** 20  # bytes written by --dump-outputs in all
+
+
+def dump_sites_total(m, S, solves, world):
+    """Sites --dump-outputs samples per solve over all ranks: DUMP_SITES, or fewer where the files would pass DUMP_LIMIT
+    (per site and solve: X_s for S shifts as float64 (re, im) pairs, plus the (rank, site) row; one residual per solve).
+    Known from the arguments alone, so every rank settles it before anything runs."""
+    per_site = solves * (S * m * 3 * 2 * 8 + 2 * 8)
+    total = min(DUMP_SITES, (DUMP_LIMIT - solves * 8) // per_site) // world * world
+    if total < world:
+        sys.exit(f"bench.py: --dump-outputs cannot fit one site per rank in {DUMP_LIMIT} bytes (m = {m}, {S} shifts)")
+    return total
+
+
+def dump_sample_sites(n_local, n_ranks, total=DUMP_SITES):
+    """The local sites --dump-outputs reads on every rank: a fixed, seeded, sorted sample (the same on every run)."""
+    import numpy as np
+    k = min(n_local, max(1, total // n_ranks))
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n_local, size=k, replace=False)).astype(np.int64)
+
+
+def sample_solutions(X, total):
+    """(sample sites of this rank, [X_s at those sites as float64 [sites, m, 3, 2] (real, imaginary) for every s])."""
+    import numpy as np
+    sites = dump_sample_sites(X[0].V, int(os.environ.get("WORLD_SIZE", "1")), total)
+    return sites, [np.stack([a.real, a.imag], axis=-1) for a in (x.download_sites(sites) for x in X)]
+
+
+def write_outputs(path, arrays):
+    """DIR/<name>.npy, float64 (dump_sites_total keeps them within DUMP_LIMIT)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def descendants(pid):
@@ -503,7 +548,13 @@ def main():
     ap.add_argument("--step-down", action="store_true",
                     help="step down the memory ladder (smaller rings, then the half-volume form) on an explicit shape too; the "
                          "default multi-GPU shape always does")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel times (HIP events in the timed region), "
+                         "the roofline and bytes moved, the exchanges' times and, on one GPU, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed sample of the solutions X_s (seeded sites) and the residual "
+                         "of the last timed step as DIR/<name>.npy (float64)")
     ap.add_argument("--generic", action="store_true", help="force the generic VALU kernels")
     ap.add_argument("--plan-only", action="store_true",
                     help="no GPU work: every rank derives its share of the run (process grid, coordinates, face messages, "
@@ -515,6 +566,8 @@ def main():
                          "(bcg_capacity_mode); the process grid then leaves x3 undivided "
                          "(default: 0 on one GPU, 32 on several with the default shape)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args, sys.argv[1:])
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -538,6 +591,7 @@ def main():
     if args.plan_only:
         return plan_only(args, world, default_shape)
 
+    import numpy as np
     import torch
     import blockcg_amd as bc
 
@@ -584,6 +638,8 @@ def main():
     lib = bc_lib.load()
     rungs = memory_ladder(world, args.local_dims, args.capacity, args.half, m, default_shape, strong,
                           True if args.step_down else None)
+    # --dump-outputs: the sample size, on every rank before any GPU work (two solves if the ladder may reach the half form)
+    dump_total = dump_sites_total(m, S, 2 if any(r["half"] for r in rungs) else 1, world) if args.dump_outputs else 0
 
     class Run:  # what one rung holds alive
         ctx = comm = D = st = X = B = None
@@ -698,27 +754,38 @@ def main():
 
     # one solve on all sites, or (half-volume form) one per site parity, each timed over exactly K iterations between barriers
     dt, bytes_in_use, residual = 0.0, 0, None
+    outputs = {}  # --dump-outputs: name -> this rank's sample
     for par in ((0, 1) if half else (None,)):
         if run.st is None and not start_solve(par):  # (the odd solve of the half-volume form: same plan as the even one)
             teardown()
             sys.exit(f"bench.py: rank {rank}: the solve of parity {par} could not be allocated")
         st = run.st
-        st.iterate(args.warmup)
+        before = st.iterate(args.warmup)
         mem_free, mem_total = torch.cuda.mem_get_info(device)  # with every field of the solve alive
         bytes_in_use = max(bytes_in_use, mem_total - mem_free)
-        ctx.profiling(True)
-        if not par:
-            ctx.profile_reset()
+        if args.full:
+            ctx.profiling(True)
+            if not par:
+                ctx.profile_reset()
         barrier()
         t0 = time.perf_counter()
-        st.iterate(args.steps)          # EXACTLY K iterations; iterate() synchronizes the stream before returning
+        done = st.iterate(args.steps) - before  # EXACTLY K iterations; iterate() synchronizes the stream before returning
         barrier()
         dt += time.perf_counter() - t0
         ctx.profiling(False)
+        if done != args.steps:
+            sys.exit(f"bench.py: rank {rank}: {done} iterations were timed, not --steps {args.steps}")
         residual = st.residual if residual is None else max(residual, st.residual)
+        if args.dump_outputs:  # X_s after the last timed step (iterate() has applied every deferred update)
+            tag = "" if par is None else ("even_" if par == 0 else "odd_")
+            sites, xs = sample_solutions(run.X, dump_total)
+            outputs[tag + "sample_sites"] = sites.astype(np.float64)
+            for s, a in enumerate(xs):
+                outputs[f"{tag}X_shift{s}"] = a
+            outputs[tag + "residual"] = np.array([st.residual], dtype=np.float64)
         st.end()  # (the even solve's fields go before the odd solve's are made)
         run.st = run.X = run.B = st = None
-    prof = ctx.profile()
+    prof = ctx.profile() if args.full else {}
     dt = over_ranks(dt, "max")
     bytes_in_use = int(over_ranks(bytes_in_use, "max"))
     comm = run.comm
@@ -727,6 +794,23 @@ def main():
         raise comm.error
     planned_now = ctx.sbcgrq_device_bytes_half(m, S, consume_B=True) if half else ctx.sbcgrq_device_bytes(m, S, consume_B=True)
     bytes_iter = ctx.bytes_per_iteration(m, S)
+    if args.dump_outputs:
+        # every rank's sample in rank order, sample_sites as (rank, local site) rows; the residual is global already
+        parts = [outputs]
+        if dist is not None:
+            parts = [None] * world if rank == 0 else None
+            dist.gather_object(outputs, parts, dst=0)
+        if rank == 0:
+            merged = {}
+            for name in outputs:
+                if name.endswith("residual"):
+                    merged[name] = outputs[name]
+                elif name.endswith("sample_sites"):
+                    merged[name] = np.concatenate([np.stack([np.full(len(p[name]), float(r)), p[name]], axis=1)
+                                                   for r, p in enumerate(parts)])
+                else:
+                    merged[name] = np.concatenate([p[name] for p in parts])
+            write_outputs(args.dump_outputs, merged)
 
     if rank == 0:
         Vg = 1
@@ -736,10 +820,6 @@ def main():
         its = K / dt
         bytes_iter_total = bytes_iter * world
         hbm_gbps = bytes_iter_total * its / 1e9
-        moved_per_gpu = sum(v.get("bytes", 0.0) for k, v in prof.items() if not k.startswith("stencil_form_")) / K
-        # (half-volume form: the PMC traffic file was taken on full-volume launches -- passing a world of 2 keeps it from being quoted)
-        roof = roofline_of(prof, list(local_dims), m, S, capacity, 2 if half else world)
-        pmc_iter = pmc_bytes_per_iteration(prof, K, list(local_dims), m, S, capacity, 2 if half else world)
         out = {
             "metric": "SBCGrQ lattice-site iterations/sec (iterations/sec x global volume), fp64",
             "value": Vg * its, "unit": "site-iter/s", "n_gpus": world, "steps": K, "warmup": args.warmup,
@@ -763,26 +843,33 @@ def main():
             # THE METRIC'S UNITS and not traffic -- since round 3 the iteration moves a third fewer bytes than that sequence of
             # passes (Q rho^-1 is not stored, the shifted systems are updated four iterations at a time).
             "hbm_GBps_algorithmic": hbm_gbps, "bytes_alg_per_iteration": bytes_iter_total,
-            # what was ACHIEVED, per GPU: the bytes this fusion has to move (sum of the per-launch algorithmic bytes of every
-            # kernel launched in the timed region) / time, and -- where profiles/hbm_traffic.json holds this shape -- the bytes
-            # the PMC counters saw the same launches move
-            "hbm_GBps_moved_per_gpu": moved_per_gpu / (dt / K) / 1e9,
-            "hbm_GBps_pmc_per_gpu": (pmc_iter / (dt / K) / 1e9) if pmc_iter else None,
-            "bytes_moved_minimum_per_iteration": moved_per_gpu * world,
-            "bytes_pmc_per_iteration": pmc_iter,
-            "hbm_frac_of_bytes_actually_moved": moved_per_gpu / (dt / K) / 1e9 / HBM_PEAK_GBPS,
-            "hbm_frac_pmc": (pmc_iter / (dt / K) / 1e9 / HBM_PEAK_GBPS) if pmc_iter else None,
             "residual_after_timed_steps": residual,
-            "kernel_ms": {k: round(v["ms"], 3) for k, v in prof.items() if not k.startswith("stencil_form_")},
-            "stencil_kernel_launches": {k[len("stencil_form_"):]: v["count"] for k, v in prof.items() if k.startswith("stencil_form_")},
             "capacity_ring_slices": capacity,
             "device_bytes_planned": planned_now,
             "device_bytes_in_use": bytes_in_use, "device_bytes_total": mem_total,  # max over ranks
-            "comm_ms_per_iteration": {k: round(v["ms"] / K, 4) for k, v in prof.items()
-                                      if k.startswith("halo_exchange") or k in ("allreduce", "pack_faces")} if world > 1 else None,
-            "roofline": roof,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:  # the figures the headline does not need: per-kernel times of the timed region, the CPU baseline
+            moved_per_gpu = sum(v.get("bytes", 0.0) for k, v in prof.items() if not k.startswith("stencil_form_")) / K
+            # (half-volume form: the PMC traffic file was taken on full-volume launches -- passing a world of 2 keeps it from being quoted)
+            roof = roofline_of(prof, list(local_dims), m, S, capacity, 2 if half else world)
+            pmc_iter = pmc_bytes_per_iteration(prof, K, list(local_dims), m, S, capacity, 2 if half else world)
+            out.update({
+                # what was ACHIEVED, per GPU: the bytes this fusion has to move (sum of the per-launch algorithmic bytes of every
+                # kernel launched in the timed region) / time, and -- where profiles/hbm_traffic.json holds this shape -- the bytes
+                # the PMC counters saw the same launches move
+                "hbm_GBps_moved_per_gpu": moved_per_gpu / (dt / K) / 1e9,
+                "hbm_GBps_pmc_per_gpu": (pmc_iter / (dt / K) / 1e9) if pmc_iter else None,
+                "bytes_moved_minimum_per_iteration": moved_per_gpu * world,
+                "bytes_pmc_per_iteration": pmc_iter,
+                "hbm_frac_of_bytes_actually_moved": moved_per_gpu / (dt / K) / 1e9 / HBM_PEAK_GBPS,
+                "hbm_frac_pmc": (pmc_iter / (dt / K) / 1e9 / HBM_PEAK_GBPS) if pmc_iter else None,
+                "kernel_ms": {k: round(v["ms"], 3) for k, v in prof.items() if not k.startswith("stencil_form_")},
+                "stencil_kernel_launches": {k[len("stencil_form_"):]: v["count"] for k, v in prof.items() if k.startswith("stencil_form_")},
+                "comm_ms_per_iteration": {k: round(v["ms"] / K, 4) for k, v in prof.items()
+                                          if k.startswith("halo_exchange") or k in ("allreduce", "pack_faces")} if world > 1 else None,
+                "roofline": roof,
+            })
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(m, S, shifts, MASS)
                 out["gpu_over_cpu_site_iter_rate"] = out["value"] / out["cpu_baseline"]["value"]

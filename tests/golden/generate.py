@@ -22,6 +22,9 @@ Files written (numpy .npz, complex128 in the reference's host layout, see oracle
   ref4d_8x8x8x8_m4.npz inputs from the oracle's counter-based generator (seeds stored), summary of
                        the reference solve only (iterations, residuals, column norms of X).
   ref1d_v96_m5.npz ref4d_4x2x4x2_m7.npz   odd block widths (the reference's N_rhs is any int), full data.
+  extra/ (single-purpose fixtures, outside the sets the parity tests iterate over):
+  extra/ref1d_v96_m4_retire.npz  eps_shifts >> eps: shifts retire early (V = 96, m = 4, 4 shifts).
+  extra/ref1d_v16_setrandom.npz  the std::rand() draws of srand(5); dirac_op D(16, 0.1) and a width-4 setRandom().
 `generate.py NAME.npz ...` writes the named fixtures only.
 """
 import os
@@ -135,6 +138,33 @@ def gen_other_solvers(name):
     print(name, "iterations CG/SCG/BCG/BCGrQ", int(d["it_cg"]), int(d["it_scg"]), int(d["it_bcg"]), int(d["it_bcgrq"]))
 
 
+def gen_shift_retirement(name):
+    """eps_shifts >> eps: shifts retire before the solve ends (inc/block_solvers.hpp:161,179-181), 1-D operator."""
+    if ONLY and name not in ONLY:
+        return
+    V, m, mass = 96, 4, 0.05
+    shifts, eps, eps_s = [0.0, 0.3, 2.0, 9.0], 1e-10, 1e-4
+    R = oracle.Reference(four_d=False)
+    U = R.make_dirac_1d(V, mass, 3)
+    B = R.field_random(m, V)
+    s = R.sbcgrq(B, shifts, eps, eps_s)
+    d = dict(dims=np.array([V]), mass=mass, shifts=np.array(shifts), eps=eps, eps_shifts=eps_s, U=U, B=B, X=s["X"],
+             iterations=np.int64(s["iterations"]), residuals=R.true_residuals(B, shifts, s["X"]))
+    np.savez(os.path.join(OUT, "extra", name), **d)
+    print(name, "iterations", int(d["iterations"]), "max residual", d["residuals"].max())
+
+
+def gen_setrandom(name):
+    """The reference's std::rand() draws: srand(5); dirac_op D(16, 0.1); then a width-4 field's setRandom()."""
+    if ONLY and name not in ONLY:
+        return
+    R = oracle.Reference(four_d=False)
+    U = R.make_dirac_1d(16, 0.1, 5)
+    B = R.field_random(4, 16)
+    np.savez(os.path.join(OUT, "extra", name), U=U, B=B, seed=np.int64(5), mass=0.1)
+    print(name, "draws", U.size + B.size)
+
+
 def main():
     if not oracle.ref_available():
         sys.exit("oracle/_ref is missing: run `make -C oracle ref` where /root/reference exists")
@@ -157,6 +187,8 @@ def main():
     # odd block widths: the reference's N_rhs is an arbitrary template int (inc/fields.hpp:19-26)
     gen_1d("ref1d_v96_m5.npz", 96, 5, 0.3, [0.0, 0.02, 0.5], 1e-10, 1e-15, 3, early=2)
     gen_nd("ref4d_4x2x4x2_m7.npz", [4, 2, 4, 2], 7, 0.15, s4, 1e-10, 1e-12, 16, early=2)
+    gen_shift_retirement("ref1d_v96_m4_retire.npz")
+    gen_setrandom("ref1d_v16_setrandom.npz")
 
 
 if __name__ == "__main__":

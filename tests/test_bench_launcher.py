@@ -306,3 +306,33 @@ def test_bare_headline_command_plans_eight_ranks():
         assert out.returncode == 0, out.stderr[-3000:]
         d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
         assert d["config"]["process_grid"] == grid and d["config"]["global_dims"] == gd and d["capacity_ring_slices"] == 32
+
+
+def test_steps_must_be_at_least_one():
+    """--steps sets the number of timed steps and ms_per_step divides by it: 0 is refused before anything starts."""
+    out = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "0", "--warmup", "1"], env=_clean_env(),
+                         capture_output=True, text=True, timeout=120)
+    assert out.returncode == 2 and "--steps must be at least 1" in out.stderr, out.stderr[-2000:]
+
+
+def test_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """--dump-outputs: the sampled sites are the same on every call (seeded), sorted, distinct and inside the local lattice,
+    split over the ranks; what is written is float64 and at most 64 MB in all."""
+    import numpy as np
+    bench = _bench_module()
+    a, b = bench.dump_sample_sites(16 ** 4, 1), bench.dump_sample_sites(16 ** 4, 1)
+    assert np.array_equal(a, b) and len(a) == bench.DUMP_SITES and np.all(np.diff(a) > 0) and 0 <= a[0] and a[-1] < 16 ** 4
+    assert len(bench.dump_sample_sites(16 ** 4, 8)) == bench.DUMP_SITES // 8 and len(bench.dump_sample_sites(100, 1)) == 100
+    bench.write_outputs(str(tmp_path / "out"), {"x": np.arange(6, dtype=np.float32).reshape(2, 3)})
+    x = np.load(tmp_path / "out" / "x.npy")
+    assert x.dtype == np.float64 and x.shape == (2, 3) and x[1, 2] == 5.0
+    # the sample size is settled from the arguments on every rank, before anything runs: the default shapes keep the full
+    # sample, wide blocks get fewer sites, and nothing ever passes 64 MB (X_s re/im + the (rank, site) rows + residuals)
+    assert bench.dump_sites_total(16, 4, 1, 1) == bench.DUMP_SITES and bench.dump_sites_total(32, 8, 2, 8) == bench.DUMP_SITES
+    for m, S, solves, world in ((16, 4, 1, 1), (32, 8, 2, 8), (512, 8, 2, 1), (4096, 8, 2, 3), (2000, 8, 1, 8)):
+        n = bench.dump_sites_total(m, S, solves, world)
+        assert n % world == 0 and n >= world
+        assert solves * (n * (S * m * 3 * 2 * 8 + 2 * 8) + 8) <= 64 * 2 ** 20
+    assert bench.dump_sites_total(512, 8, 2, 1) < bench.DUMP_SITES
+    with pytest.raises(SystemExit):  # not even one site per rank fits
+        bench.dump_sites_total(10 ** 6, 8, 2, 8)

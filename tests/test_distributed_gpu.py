@@ -195,18 +195,63 @@ print("RCCL_VIEW_OK")
     assert out.returncode == 0 and "RCCL_VIEW_OK" in out.stdout, out.stdout[-2000:] + out.stderr[-3000:]
 
 
-def test_bench_two_ranks_on_one_gpu():
-    """bench.py's multi-rank path end to end (gloo, both ranks on GPU 0, small local volume)."""
+def test_bench_two_ranks_on_one_gpu(tmp_path):
+    """bench.py's multi-rank path end to end (gloo, both ranks on GPU 0, small local volume); --dump-outputs gathers both
+    ranks' samples on rank 0."""
     env = dict(os.environ, BCG_BACKEND="gloo", BCG_DEVICE="0", OMP_NUM_THREADS="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", "29652", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--local-dims", "16", "16", "16", "16"]
+           "--local-dims", "16", "16", "16", "16", "--dump-outputs", str(tmp_path / "out")]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     import json
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]
     d = json.loads(line)
     assert d["n_gpus"] == 2 and d["steps"] == 3 and d["value"] > 0 and d["config"]["global_dims"] == [16, 16, 16, 32]
+    dumped = _dumped(tmp_path / "out")
+    assert dumped["X_shift0"].shape == (2048, 16, 3, 2) and sorted(set(dumped["sample_sites"][:, 0])) == [0.0, 1.0]
+
+
+def _bench_line(cmd, env):
+    import json
+    out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+def _dumped(path):
+    import glob
+    import numpy as np
+    return {os.path.basename(f)[:-4]: np.load(f) for f in sorted(glob.glob(os.path.join(path, "*.npy")))}
+
+
+def test_bench_plain_full_and_dump_outputs(tmp_path):
+    """One GPU, small lattice.  A plain run times exactly --steps iterations and carries no per-kernel figures; --full adds
+    them; --dump-outputs writes the solutions at the seeded sample sites and the residual, float64, the same from run to run."""
+    import numpy as np
+    env = dict(os.environ, OMP_NUM_THREADS="1")
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+            "--local-dims", "16", "16", "16", "16"]
+    runs = []
+    for k in range(2):
+        d = _bench_line(base + ["--dump-outputs", str(tmp_path / f"run{k}")], env)
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+        assert d["unit"] == "site-iter/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+        assert d["value"] == pytest.approx(16 ** 4 * 1e3 / d["ms_per_step"])
+        assert not {"kernel_ms", "roofline", "cpu_baseline", "comm_ms_per_iteration"} & set(d)
+        runs.append(_dumped(tmp_path / f"run{k}"))
+    a, b = runs
+    assert sorted(a) == ["X_shift0", "X_shift1", "X_shift2", "X_shift3", "residual", "sample_sites"]
+    assert all(v.dtype == np.float64 for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 * 2 ** 20
+    assert a["X_shift0"].shape == (2048, 16, 3, 2) and a["sample_sites"].shape == (2048, 2)
+    assert np.all(a["sample_sites"][:, 0] == 0) and np.all(np.diff(a["sample_sites"][:, 1]) > 0)
+    assert np.all(np.isfinite(a["X_shift0"])) and np.abs(a["X_shift0"]).max() > 0 and np.isfinite(a["residual"][0])
+    for name in a:
+        np.testing.assert_allclose(a[name], b[name], rtol=0, atol=1e-12 * np.abs(b[name]).max())
+    d = _bench_line(base + ["--full", "--no-cpu-baseline"], env)
+    assert d["steps"] == 3 and d["kernel_ms"] and d["roofline"] and d["hbm_GBps_moved_per_gpu"] > 0
 
 
 def test_bench_ranks_on_one_gpu_native_transport():
@@ -236,7 +281,7 @@ def test_bare_bench_command_starts_its_own_ranks(gpus):
     env.update(BCG_BACKEND="rccl", BCG_RCCL_LIB=_mock_transport(), BCG_DEVICE="0", OMP_NUM_THREADS="1", BCG_HOP_BLOCKS="32",
                BCG_HOP_PATCH="16,2,2", BCG_BENCH_TIMEOUT="500")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "3", "--warmup", "1",
-           "--local-dims", "32", "8", "8", "8", "--capacity", "4"]
+           "--local-dims", "32", "8", "8", "8", "--capacity", "4", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     _sweep_mock_files()
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
@@ -262,7 +307,7 @@ def test_bare_bench_command_half_volume_option():
     env.update(BCG_BACKEND="rccl", BCG_RCCL_LIB=_mock_transport(), BCG_DEVICE="0", OMP_NUM_THREADS="1", BCG_HOP_BLOCKS="32",
                BCG_HOP_PATCH="16,2,2", BCG_BENCH_TIMEOUT="500", BCG_HALF_CHUNK="2")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--half", "--steps", "4", "--warmup", "1",
-           "--local-dims", "64", "8", "8", "6"]
+           "--local-dims", "64", "8", "8", "6", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     _sweep_mock_files()
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
@@ -287,7 +332,8 @@ def test_bare_bench_command_strong_scaling_ladder():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(BCG_BACKEND="rccl", BCG_RCCL_LIB=_mock_transport(), BCG_DEVICE="0", OMP_NUM_THREADS="1", BCG_HOP_BLOCKS="32",
                BCG_HOP_PATCH="16,2,2", BCG_BENCH_TIMEOUT="500", BCG_BENCH_STRONG_DIMS="32,8,16,16")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--ladder", "strong", "--steps", "4", "--warmup", "1"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--ladder", "strong", "--steps", "4", "--warmup", "1",
+           "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     _sweep_mock_files()
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]

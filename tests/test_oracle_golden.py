@@ -9,7 +9,7 @@ import os
 import numpy as np
 import pytest
 
-from conftest import TOL_KERNEL, TOL_SOLUTION, golden_files, rel_err
+from conftest import TOL_KERNEL, TOL_SOLUTION, golden_files, load_golden, rel_err
 
 FULL = [f for f in golden_files() if "8x8x8x8" not in f and "other_solvers" not in f]
 WITH_PRIMS = [f for f in FULL if "v1000" not in f]
@@ -128,23 +128,25 @@ def test_other_solvers_match_reference(orc):
 
 
 def test_shift_retirement_against_live_reference(orc):
-    """eps_shifts >> eps: shifts retire early (inc/block_solvers.hpp:161,179-181).  Needs oracle/_ref (the unmodified
-    reference built from /root/reference); compares iteration count, frozen shifted solutions and residuals."""
+    """eps_shifts >> eps: shifts retire early (inc/block_solvers.hpp:161,179-181).  Against the unmodified reference's run
+    stored in tests/golden/extra/ref1d_v96_m4_retire.npz (and, where oracle/_ref is built, against the live reference
+    too); compares iteration count, frozen shifted solutions and residuals."""
     import oracle
-    if not oracle.ref_available():
-        pytest.skip("oracle/_ref not built")
-    R = oracle.Reference(four_d=False)
-    V, m, mass = 96, 4, 0.05
-    shifts, eps, eps_s = [0.0, 0.3, 2.0, 9.0], 1e-10, 1e-4
-    U = R.make_dirac_1d(V, mass, 3)
-    B = R.field_random(m, V)
-    ref = R.sbcgrq(B, shifts, eps, eps_s)
+    g = load_golden(os.path.join("extra", "ref1d_v96_m4_retire.npz"))
+    V, mass, U, B = int(g["dims"][0]), float(g["mass"]), g["U"], g["B"]
+    shifts, eps, eps_s = list(g["shifts"]), float(g["eps"]), float(g["eps_shifts"])
+    ref = {"iterations": int(g["iterations"]), "X": g["X"], "residuals": g["residuals"]}
+    if oracle.ref_available():
+        R = oracle.Reference(four_d=False)
+        assert np.array_equal(R.make_dirac_1d(V, mass, 3), U) and np.array_equal(R.field_random(B.shape[1], V), B)
+        live = R.sbcgrq(B, shifts, eps, eps_s)
+        assert live["iterations"] == ref["iterations"] and rel_err(live["X"], ref["X"]) < 1e-12
     got = orc.sbcgrq(U, [V], mass, B, shifts, eps, eps_s, trace_limit=2000)
     assert got["iterations"] == ref["iterations"]
     assert rel_err(got["X"], ref["X"]) < 1e-9
     visited = got["trace"]["residual_shift"] >= 0
     assert visited[0, 1:].all() and not visited[-1, 1:].all()   # all shifts start active, some retire before the end
-    assert rel_err(orc.true_residuals(U, [V], mass, B, shifts, got["X"]), R.true_residuals(B, shifts, ref["X"])) < 1e-6
+    assert rel_err(orc.true_residuals(U, [V], mass, B, shifts, got["X"]), ref["residuals"]) < 1e-6
 
 
 def test_nd_operator_against_the_reference_1d_operator_line_by_line(orc):

@@ -7,7 +7,7 @@ out=gpurun_out/prof_other
 rm -rf $out; mkdir -p $out
 run() {  # tag, bench args...
   tag=$1; shift
-  rocprofv3 --kernel-trace --stats --output-format csv -d $out/$tag -- python bench.py --no-cpu-baseline "$@" > $out/${tag}_bench.json 2> $out/$tag.err || { tail -3 $out/$tag.err; return 1; }
+  rocprofv3 --kernel-trace --stats --output-format csv -d $out/$tag -- python bench.py --full --no-cpu-baseline "$@" > $out/${tag}_bench.json 2> $out/$tag.err || { tail -3 $out/$tag.err; return 1; }
   find $out/$tag -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $out/${tag}_kernel_stats.csv
   python - "$out/${tag}_bench.json" <<'PY'
 import json,sys

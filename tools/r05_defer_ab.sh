@@ -3,7 +3,7 @@
 out=gpurun_out/r05; mkdir -p $out
 {
 for rep in 1 2 3; do for d in 1 0; do
-  echo "-- bench BCG_DEFER_X0=$d: $(BCG_DEFER_X0=$d python bench.py --no-cpu-baseline --steps 24 --warmup 4 2>/dev/null | python -c "
+  echo "-- bench BCG_DEFER_X0=$d: $(BCG_DEFER_X0=$d python bench.py --full --no-cpu-baseline --steps 24 --warmup 4 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); n=d['steps']
 print('ms/step %.2f' % d['ms_per_step'], {k: round(v/n,2) for k,v in d['kernel_ms'].items()})")"
