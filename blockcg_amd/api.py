@@ -309,29 +309,15 @@ class dirac_op:
             self.ctx.check(self.ctx.lib.bcg_dirac_hop(self.ctx.h, self.h, lhs.h, rhs.h))
 
 
-def SBCGrQ(X, B, D, sigma, eps=1.e-15, eps_shifts=1.e-15, max_iterations=1000000, trace_limit=0, consume_B=False,
-           return_info=False):
-    """inc/block_solvers.hpp:91-185.  X: list of fields (overwritten); returns operator applications."""
-    ctx = B.ctx
-    S = len(X)
-    if len(sigma) != S:
-        raise ValueError("number of shifts does not match number of solution vectors")  # :97-98
-    m = B.N_rhs
-    sig = np.ascontiguousarray(sigma, dtype=np.float64)
-    Xh = (ctypes.c_void_p * S)(*[x.h for x in X])
-    it = ctypes.c_int(0)
-    res = ctypes.c_double(0.0)
-    tr = None
-    tr_p = None
-    if trace_limit > 0:
-        mats = np.zeros((trace_limit, 3 + 2 * S, m, m), dtype=np.complex128)
-        rr = np.zeros((trace_limit, 1 + S), dtype=np.float64)
-        tr = _lib.bcg_sbcgrq_trace(trace_limit, 0, _dp(mats), _dp(rr))
-        tr_p = ctypes.byref(tr)
-    ctx.check(ctx.lib.bcg_sbcgrq_solve(ctx.h, D.h, D.mass, Xh, B.h, S, _dp(sig), eps, eps_shifts, int(max_iterations),
-                                       1 if consume_B else 0, ctypes.byref(it), ctypes.byref(res), tr_p))
-    if not return_info:
-        return it.value
+def _trace_buffers(trace_limit, S, m):
+    if trace_limit <= 0:
+        return None, None, None
+    mats = np.zeros((trace_limit, 3 + 2 * S, m, m), dtype=np.complex128)
+    rr = np.zeros((trace_limit, 1 + S), dtype=np.float64)
+    return _lib.bcg_sbcgrq_trace(trace_limit, 0, _dp(mats), _dp(rr)), mats, rr
+
+
+def _solve_info(it, res, tr, mats, rr, S):
     info = dict(iterations=it.value, residual=res.value, trace=None)
     if tr is not None:
         n = tr.recorded
@@ -339,6 +325,53 @@ def SBCGrQ(X, B, D, sigma, eps=1.e-15, eps_shifts=1.e-15, max_iterations=1000000
         info["trace"] = dict(alpha=mt[:, 0], rho=mt[:, 1], delta=mt[:, 2], alpha_s=mt[:, 3:3 + S],
                              beta_s=mt[:, 3 + S:3 + 2 * S], residual=rr[:n, 0], residual_shift=rr[:n, 1:])
     return info
+
+
+def SBCGrQ(X, B, D, sigma, eps=1.e-15, eps_shifts=1.e-15, max_iterations=1000000, trace_limit=0, consume_B=False,
+           return_info=False):
+    """inc/block_solvers.hpp:91-185.  X: list of fields (overwritten); returns operator applications."""
+    ctx = B.ctx
+    S = len(X)
+    if len(sigma) != S:
+        raise ValueError("number of shifts does not match number of solution vectors")  # :97-98
+    sig = np.ascontiguousarray(sigma, dtype=np.float64)
+    Xh = (ctypes.c_void_p * S)(*[x.h for x in X])
+    it = ctypes.c_int(0)
+    res = ctypes.c_double(0.0)
+    tr, mats, rr = _trace_buffers(trace_limit, S, B.N_rhs)
+    ctx.check(ctx.lib.bcg_sbcgrq_solve(ctx.h, D.h, D.mass, Xh, B.h, S, _dp(sig), eps, eps_shifts, int(max_iterations),
+                                       1 if consume_B else 0, ctypes.byref(it), ctypes.byref(res),
+                                       ctypes.byref(tr) if tr is not None else None))
+    if not return_info:
+        return it.value
+    return _solve_info(it, res, tr, mats, rr, S)
+
+
+def _sum_args(sigma, residues):
+    sig = np.ascontiguousarray(sigma, dtype=np.float64)
+    a = np.ascontiguousarray(residues, dtype=np.float64)
+    if a.shape != sig.shape:
+        raise ValueError("one residue per shift is needed")
+    return sig, a
+
+
+def SBCGrQ_sum(Y, B, D, sigma, residues, c0=0.0, eps=1.e-15, eps_shifts=1.e-15, max_iterations=1000000, trace_limit=0,
+               consume_B=False, return_info=False):
+    """Y = c0 B + sum_s residues[s] (A + sigma_s)^-1 B: the partial-fraction form of a rational function of the operator.
+    The solve is SBCGrQ's (same iterations, coefficients and trace, bit for bit), but the shifted solutions are summed into
+    the one field Y as they are updated instead of being kept (include/blockcg_hip.h, bcg_sbcgrq_solve_sum)."""
+    ctx = B.ctx
+    sig, a = _sum_args(sigma, residues)
+    S = len(sig)
+    it = ctypes.c_int(0)
+    res = ctypes.c_double(0.0)
+    tr, mats, rr = _trace_buffers(trace_limit, S, B.N_rhs)
+    ctx.check(ctx.lib.bcg_sbcgrq_solve_sum(ctx.h, D.h, D.mass, Y.h, B.h, S, _dp(sig), _dp(a), float(c0), eps, eps_shifts,
+                                           1 if consume_B else 0, int(max_iterations), ctypes.byref(it), ctypes.byref(res),
+                                           ctypes.byref(tr) if tr is not None else None))
+    if not return_info:
+        return it.value
+    return _solve_info(it, res, tr, mats, rr, S)
 
 
 class SBCGrQState:
@@ -377,6 +410,21 @@ class SBCGrQState:
             self.end()
         except Exception:
             pass
+
+
+class SBCGrQSumState(SBCGrQState):
+    """SBCGrQState in sum mode (bcg_sbcgrq_begin_sum): Y accumulates c0 B + sum_s residues[s] X_s."""
+
+    def __init__(self, Y, B, D, sigma, residues, c0=0.0, eps=0.0, eps_shifts=0.0, consume_B=False):
+        self.ctx = B.ctx
+        self._keep = (Y, B, D)
+        sig, a = _sum_args(sigma, residues)
+        st = ctypes.c_void_p()
+        self.ctx.check(self.ctx.lib.bcg_sbcgrq_begin_sum(self.ctx.h, D.h, D.mass, Y.h, B.h, len(sig), _dp(sig), _dp(a),
+                                                         float(c0), eps, eps_shifts, 1 if consume_B else 0, ctypes.byref(st)))
+        self.h = st
+        self.iterations = 0
+        self.residual = 1.0
 
 
 def true_residuals(X, B, D, sigma):

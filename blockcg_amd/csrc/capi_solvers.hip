@@ -55,13 +55,14 @@ int phase_B(bcg_context* c, bcg_field* Q, const bcg_field* T, const CMat& alpha,
 // (:152 second half, :145, :158, :175, :177)
 int trisolve(bcg_context* c, bcg_field* y, const CMat& R);
 // rinv_out != nullptr (lazy_q_width): Q rho^-1 is used but not stored; *rinv_out = rho^-1 for the next phase B
+// Y != nullptr (sum mode, SBCGrQ_sum below): X is not read; Y += P_s A_s for every s instead (the A_s carry the residues)
 int phase_C(bcg_context* c, bcg_field* Q, const CMat& rho, bcg_field* const* X, bcg_field* const* P, int n,
-            const std::vector<CMat>& A, const std::vector<CMat>& Bm, CMat* rinv_out = nullptr) {
+            const std::vector<CMat>& A, const std::vector<CMat>& Bm, CMat* rinv_out = nullptr, bcg_field* Y = nullptr) {
   const int m = Q->m;
   if (!fast_rmul(c, m)) {
     BCG_TRY(trisolve(c, Q, rho));
     for (int s = 0; s < n; ++s) {
-      BCG_TRY(rmul(c, X[s], P[s], A[s], 0.0, bcg::RMUL_ADD, "block_axpy"));
+      BCG_TRY(rmul(c, Y ? Y : X[s], P[s], A[s], 0.0, bcg::RMUL_ADD, "block_axpy"));
       BCG_TRY(rmul(c, P[s], Q, Bm[s], 1.0, bcg::RMUL_XPAY, "block_xpay"));
     }
     return BCG_OK;
@@ -78,16 +79,17 @@ int phase_C(bcg_context* c, bcg_field* Q, const CMat& rho, bcg_field* const* X, 
     for (int k = 0; k < ns; ++k) {
       mats.push_back(&A[s0 + k]);
       mats.push_back(&Bm[s0 + k]);
-      Xp[k] = X[s0 + k]->d;
+      Xp[k] = Y ? nullptr : X[s0 + k]->d;
       Pp[k] = P[s0 + k]->d;
     }
     const double2* Md;
     BCG_TRY(upload_mats(c, m, mats.data(), static_cast<int>(mats.size()), &Md));
     {
-      // the launch that applies rho^-1 reads and writes Q; a later launch of the same iteration (m = 32) re-reads it
-      ProfScope ps(c, "phaseC", row_bytes(Q, (first && !rinv_out ? 2 : 1) + 4 * ns),
+      // the launch that applies rho^-1 reads and writes Q; a later launch of the same iteration (m = 32) re-reads it.
+      // Sum mode: Y read and written once per launch instead of the X_s (2 + 2 ns rows for 4 ns)
+      ProfScope ps(c, Y ? "phaseC_sum" : "phaseC", row_bytes(Q, (first && !rinv_out ? 2 : 1) + (Y ? 2 * ns + (ns > 0 ? 2 : 0) : 4 * ns)),
                    product_flops(Q, (rinv_out || first ? 1 : 0) + 2 * ns));
-      bcg::launch_phaseC(c->stream, m, rows_of(Q), Q->d, Xp, Pp, ns, Md, rinv_out ? 2 : first, c->row_blocks_C);
+      bcg::launch_phaseC(c->stream, m, rows_of(Q), Q->d, Xp, Pp, ns, Md, rinv_out ? 2 : first, c->row_blocks_C, Y ? Y->d : nullptr);
     }
     BCG_TRY(check_launch(c, "phaseC"));
   }
@@ -184,10 +186,11 @@ DeferredX0 compose_x0(const std::vector<DeferredIteration>& pend) {
 // paths, sbcgrq_flush_pending): only the shifts >= 1 are touched, *flush_rinv is its rho^-1 and rho_new, A0, B0 are unused.
 // p0_first != nullptr: the group's X_0 updates were deferred (DeferredX0); they are added from that field (the group's first
 // P_0) and the normalised residual blocks in the launch that takes entry 0
+// Y != nullptr (sum mode): every entry's X updates, the composed X_0 ones included, go into Y (X is not read)
 int phase_C_multi(bcg_context* c, const std::vector<DeferredIteration>& pend, bcg_field* Qnew, const CMat& rho_new,
                   bcg_field* const* X, bcg_field* const* P, const CMat& A0, const CMat& B0, int n_active_new,
                   const std::vector<CMat>& Anew, const std::vector<CMat>& Bnew, CMat* rinv_out, bool lazy,
-                  const CMat* flush_rinv = nullptr, const bcg_field* p0_first = nullptr) {
+                  const CMat* flush_rinv = nullptr, const bcg_field* p0_first = nullptr, bcg_field* Y = nullptr) {
   const int m = Qnew->m, ns = static_cast<int>(pend.size()) + 1;
   const CMat rinv_new = flush_rinv ? *flush_rinv : (lazy ? bcg::upper_triangular_inverse(rho_new) : CMat());
   const double2* Qd[4];
@@ -204,7 +207,7 @@ int phase_C_multi(bcg_context* c, const std::vector<DeferredIteration>& pend, bc
     entries.push_back(Entry{0, ns - 1, ns, {&A0, &B0}});
   } else {
     const std::vector<CMat> a0(1, A0), b0(1, B0);
-    BCG_TRY(phase_C(c, Qnew, rho_new, X, P, 1, a0, b0, nullptr));  // Q <- Q rho^-1 stored; shift 0
+    BCG_TRY(phase_C(c, Qnew, rho_new, X, P, 1, a0, b0, nullptr, Y));  // Q <- Q rho^-1 stored; shift 0
   }
   const int n_first = ns > 1 ? pend[0].n_active : n_active_new;
   for (int s = 1; s < n_first; ++s) {  // the active set only shrinks: a shift takes a prefix of the steps
@@ -232,6 +235,7 @@ int phase_C_multi(bcg_context* c, const std::vector<DeferredIteration>& pend, bc
     for (const CMat& M : x0.mats) entries[0].mats.push_back(&M);
   }
   static const char* const names[5] = {"", "", "phaseC_multi2", "phaseC_multi3", "phaseC_multi4"};
+  static const char* const sum_names[5] = {"", "", "phaseC_multi2_sum", "phaseC_multi3_sum", "phaseC_multi4_sum"};
   for (size_t e0 = 0; e0 < entries.size();) {
     const bool with_x0 = xacc > 0 && e0 == 0;
     // as many entries as have LDS room for their matrices beside the rinv_j (m = 16: four shifts at any depth, eight at
@@ -253,7 +257,7 @@ int phase_C_multi(bcg_context* c, const std::vector<DeferredIteration>& pend, bc
     double products = lazy ? ns : 0;
     for (int k = 0; k < n; ++k) {
       const Entry& e = entries[e0 + k];
-      Xp[k] = X[e.shift]->d;
+      Xp[k] = Y ? nullptr : X[e.shift]->d;
       Pp[k] = P[e.shift]->d;
       first[k] = e.first;
       last[k] = e.last;
@@ -265,10 +269,11 @@ int phase_C_multi(bcg_context* c, const std::vector<DeferredIteration>& pend, bc
     {
       // one profile entry per group size: each is its own kernel instantiation (k_phaseC_multi<m, waves, ns>)
       const double2* const p1 = (with_x0 && p0_first) ? p0_first->d : nullptr;
-      // (the unread slot of the spare-less form is no product)
-      ProfScope ps(c, names[ns], row_bytes(Qnew, ns + 4 * n + (p1 ? 1 : 0)), product_flops(Qnew, products - ((with_x0 && !p1) ? 1 : 0)));
+      // (the unread slot of the spare-less form is no product; sum mode: Y read and written once, 2 n + 2 rows for 4 n)
+      ProfScope ps(c, Y ? sum_names[ns] : names[ns], row_bytes(Qnew, ns + (Y ? 2 * n + 2 : 4 * n) + (p1 ? 1 : 0)),
+                   product_flops(Qnew, products - ((with_x0 && !p1) ? 1 : 0)));
       bcg::launch_phaseC_multi(c->stream, m, rows_of(Qnew), ns, Qd, Xp, Pp, n, first, last, Md, c->row_blocks_C, lazy,
-                               with_x0 ? xacc : 0, p1);
+                               with_x0 ? xacc : 0, p1, Y ? Y->d : nullptr);
     }
     BCG_TRY(check_launch(c, "phaseC_multi"));
     e0 += n;
@@ -546,7 +551,9 @@ struct bcg_sbcgrq_state {
   int m = 0, n_shifts = 0;
   std::vector<double> sigma;
   double eps = 0.0, eps_shifts = 0.0;
-  std::vector<bcg_field*> X;
+  std::vector<bcg_field*> X;             // (sum mode: none, all nullptr)
+  bcg_field* Y = nullptr;                // sum mode: Y = c0 B + sum_s residue[s] X_s is accumulated here
+  std::vector<double> residue;
   bcg_field* B = nullptr;
   bcg_field* T = nullptr;
   bcg_field* Q = nullptr;
@@ -603,7 +610,9 @@ int sbcgrq_iteration(bcg_sbcgrq_state* st, bcg_sbcgrq_trace* trace, bool more_fo
   BCG_TRY(phase_A(c, st->g, st->mass, sigma[0], st->T, st->P[0], st->alpha_inv));  // global reduction #1
   if (!st->alpha_inv.all_finite()) BCG_FAIL(c, BCG_ERR_NUMERIC, "SBCGrQ: P^dagger A P is not finite");
   st->alpha = bcg::inverse_full_pivot(st->alpha_inv);    // :142
-  const CMat alpha_delta = st->alpha * st->delta;        // :145 uses delta of the previous iteration
+  // :145 uses delta of the previous iteration.  Sum mode: every X_s update is Y += P_s (a_s M) -- the residue folded into
+  // the coefficient here, so that the deferred and composed forms below carry it too (they are linear in the coefficients)
+  const CMat alpha_delta = st->Y ? st->residue[0] * (st->alpha * st->delta) : st->alpha * st->delta;
   // Q -= T alpha ; Gram matrix of the new Q                                  :148, :152
   CMat G2;
   if (!st->pending.empty()) {  // the old block is needed by a later phase C: the new one goes to another buffer
@@ -658,7 +667,7 @@ int sbcgrq_iteration(bcg_sbcgrq_state* st, bcg_sbcgrq_trace* trace, bool more_fo
     st->beta_s[s] = bcg::inverse_full_pivot(beta_s_inv);                                                 // :166
     st->alpha_s[s] = st->beta_s[s] * st->alpha * st->rho_old * st->alpha_inv_old * st->alpha_s[s];       // :167-168
     const double residual_shift = max_ratio((st->rho * st->alpha_inv * st->alpha_s[s]).row_norms(), st->b_norm);  // :169-172
-    Acoef.push_back(st->alpha_s[s]);                                                                     // :175
+    Acoef.push_back(st->Y ? st->residue[s] * st->alpha_s[s] : st->alpha_s[s]);                           // :175
     Bcoef.push_back(st->beta_s[s] * rho_dag);                                                            // :177
     A_by_shift[s] = Acoef.back();
     B_by_shift[s] = Bcoef.back();
@@ -716,7 +725,7 @@ int sbcgrq_iteration(bcg_sbcgrq_state* st, bcg_sbcgrq_trace* trace, bool more_fo
       d.A0 = alpha_delta;
       d.R0 = rho_dag;
     } else {
-      BCG_TRY(phase_C(c, st->Q, st->rho, Xa.data(), Pa.data(), 1, Acoef, Bcoef, lazy ? &st->q_rinv : nullptr));
+      BCG_TRY(phase_C(c, st->Q, st->rho, Xa.data(), Pa.data(), 1, Acoef, Bcoef, lazy ? &st->q_rinv : nullptr, st->Y));
     }
     d.Q = st->Q;
     d.rinv = st->q_rinv;
@@ -728,7 +737,7 @@ int sbcgrq_iteration(bcg_sbcgrq_state* st, bcg_sbcgrq_trace* trace, bool more_fo
     std::vector<DeferredIteration> pend;
     pend.swap(st->pending);  // whatever happens below, these updates are not applied a second time (sbcgrq_flush_pending)
     const int rc = phase_C_multi(c, pend, st->Q, st->rho, st->X.data(), st->P.data(), alpha_delta, rho_dag, n_active,
-                                 A_by_shift, B_by_shift, lazy ? &st->q_rinv : nullptr, lazy, nullptr, st->P0_first);
+                                 A_by_shift, B_by_shift, lazy ? &st->q_rinv : nullptr, lazy, nullptr, st->P0_first, st->Y);
     for (const DeferredIteration& d : pend) {
       if (!st->T) st->T = d.Q;
       else st->Qfree.push_back(d.Q);
@@ -740,7 +749,7 @@ int sbcgrq_iteration(bcg_sbcgrq_state* st, bcg_sbcgrq_trace* trace, bool more_fo
     BCG_TRY(rc);
   } else {
     BCG_TRY(phase_C(c, st->Q, st->rho, Xa.data(), Pa.data(), static_cast<int>(Xa.size()), Acoef, Bcoef,
-                    lazy ? &st->q_rinv : nullptr));
+                    lazy ? &st->q_rinv : nullptr, st->Y));
   }
   st->q_lazy = lazy;  // from now on the stored Q is un-normalised: Q_true = Q q_rinv
   if (tracing) trace->recorded += 1;
@@ -771,35 +780,37 @@ int sbcgrq_flush_pending(bcg_sbcgrq_state* st) {
       for (int k = 0; k < ns; ++k) {
         mats.push_back(&last.A[s0 + k]);
         mats.push_back(&last.B[s0 + k]);
-        Xp[k] = st->X[s0 + k]->d;
+        Xp[k] = st->Y ? nullptr : st->X[s0 + k]->d;
         Pp[k] = st->P[s0 + k]->d;
       }
       const double2* Md;
       rc = upload_mats(c, m, mats.data(), static_cast<int>(mats.size()), &Md);
       if (rc != BCG_OK) break;
-      bcg::launch_phaseC(c->stream, m, rows_of(last.Q), last.Q->d, Xp, Pp, ns, Md, lazy ? 2 : 0, c->row_blocks_C);
+      bcg::launch_phaseC(c->stream, m, rows_of(last.Q), last.Q->d, Xp, Pp, ns, Md, lazy ? 2 : 0, c->row_blocks_C,
+                         st->Y ? st->Y->d : nullptr);
       rc = check_launch(c, "phaseC");
       s0 += ns;
     }
   } else {
     const CMat none;
     rc = phase_C_multi(c, pend, last.Q, none, st->X.data(), st->P.data(), none, none, last.n_active, last.A, last.B, nullptr,
-                       lazy, &last.rinv);
+                       lazy, &last.rinv, nullptr, st->Y);
   }
   pend.push_back(last);
+  bcg_field* const X0 = st->Y ? st->Y : st->X[0];  // (sum mode: the coefficients carry residue[0])
   // ... and X_0's, where they waited too: X_0 += P_0^(0) C + sum_k Q_k (rinv_k D_k), over ALL pending iterations (no
   // closing iteration follows: the sum over q_k runs to the last but one, the last one's q only entered the current P_0)
   if (rc == BCG_OK && pend[0].x0_deferred && pend[0].x0_backward) {
     // the spare-less form: one iteration pending, its P_0 gone -- X_0 += (P_0^(1) - q_0) M with the current P_0 (the failed
     // iteration has not touched it) and M = R_0^-1 A_0
     const CMat M = pend[0].rinv.adjoint() * pend[0].A0;
-    rc = rmul(c, st->X[0], st->P[0], M, 0.0, bcg::RMUL_ADD, "block_axpy");
-    if (rc == BCG_OK) rc = rmul(c, st->X[0], pend[0].Q, -(pend[0].rinv * M), 0.0, bcg::RMUL_ADD, "block_axpy");
+    rc = rmul(c, X0, st->P[0], M, 0.0, bcg::RMUL_ADD, "block_axpy");
+    if (rc == BCG_OK) rc = rmul(c, X0, pend[0].Q, -(pend[0].rinv * M), 0.0, bcg::RMUL_ADD, "block_axpy");
   } else if (rc == BCG_OK && st->P0_first && pend[0].x0_deferred) {
     const DeferredX0 x0 = compose_x0(pend);
-    rc = rmul(c, st->X[0], st->P0_first, x0.mats[0], 0.0, bcg::RMUL_ADD, "block_axpy");
+    rc = rmul(c, X0, st->P0_first, x0.mats[0], 0.0, bcg::RMUL_ADD, "block_axpy");
     for (size_t k = 0; k + 1 < x0.mats.size() && rc == BCG_OK; ++k)
-      rc = rmul(c, st->X[0], pend[k].Q, pend[k].rinv * x0.mats[k + 1], 0.0, bcg::RMUL_ADD, "block_axpy");
+      rc = rmul(c, X0, pend[k].Q, pend[k].rinv * x0.mats[k + 1], 0.0, bcg::RMUL_ADD, "block_axpy");
   }
   if (st->P0_first) {
     st->P0_spare = st->P0_first;
@@ -814,17 +825,22 @@ int sbcgrq_flush_pending(bcg_sbcgrq_state* st) {
   return rc;
 }
 
-}  // namespace
-
-extern "C" {
-
-int bcg_sbcgrq_begin(bcg_context* c, const bcg_gauge* g, double mass, bcg_field* const* X, bcg_field* B, int n_shifts,
-                     const double* sigma, double eps, double eps_shifts, int consume_B, bcg_sbcgrq_state** out) {
-  DeviceScope on_device(c);
-  if (!c || !g || !X || !B || !sigma || !out || n_shifts < 1 || g->ctx != c || B->ctx != c) return BCG_ERR_INVALID;
+// Sum mode (Y != nullptr; bcg_sbcgrq_begin_sum): X is not given, Y = c0 B + sum_s residue[s] X_s is accumulated instead
+int sbcgrq_begin(bcg_context* c, const bcg_gauge* g, double mass, bcg_field* const* X, bcg_field* B, int n_shifts,
+                 const double* sigma, double eps, double eps_shifts, int consume_B, bcg_sbcgrq_state** out, bcg_field* Y,
+                 const double* residue, double c0) {
+  if (!c || !g || !(X || Y) || !B || !sigma || !out || n_shifts < 1 || g->ctx != c || B->ctx != c) return BCG_ERR_INVALID;
   const int m = B->m;
-  for (int s = 0; s < n_shifts; ++s)
-    if (!same_shape(X[s], B) || X[s] == B) BCG_FAIL(c, BCG_ERR_INVALID, "SBCGrQ: X[s] must be distinct fields of B's width");
+  if (Y) {
+    if (!same_shape(Y, B) || Y == B) BCG_FAIL(c, BCG_ERR_INVALID, "SBCGrQ_sum: Y must be a field of B's width and parity, distinct from B");
+    if (!residue) BCG_FAIL(c, BCG_ERR_INVALID, "SBCGrQ_sum: one residue per shift is needed");
+    if (!std::isfinite(c0)) BCG_FAIL(c, BCG_ERR_INVALID, "SBCGrQ_sum: c0 is not finite");
+    for (int s = 0; s < n_shifts; ++s)
+      if (!std::isfinite(residue[s])) BCG_FAIL(c, BCG_ERR_INVALID, "SBCGrQ_sum: a residue is not finite");
+  } else {
+    for (int s = 0; s < n_shifts; ++s)
+      if (!same_shape(X[s], B) || X[s] == B) BCG_FAIL(c, BCG_ERR_INVALID, "SBCGrQ: X[s] must be distinct fields of B's width");
+  }
   // :97-101
   if (sigma[0] < 0.0) BCG_FAIL(c, BCG_ERR_INVALID, "SBCGrQ: shifts must be zero or positive");
   if (!std::is_sorted(sigma, sigma + n_shifts)) BCG_FAIL(c, BCG_ERR_INVALID, "SBCGrQ: shifts must be in ascending order");
@@ -838,7 +854,13 @@ int bcg_sbcgrq_begin(bcg_context* c, const bcg_gauge* g, double mass, bcg_field*
   st->sigma.assign(sigma, sigma + n_shifts);
   st->eps = eps;
   st->eps_shifts = eps_shifts;
-  st->X.assign(X, X + n_shifts);
+  if (Y) {
+    st->X.assign(n_shifts, nullptr);
+    st->Y = Y;
+    st->residue.assign(residue, residue + n_shifts);
+  } else {
+    st->X.assign(X, X + n_shifts);
+  }
   st->B = B;
   st->n_unconverged = n_shifts;                  // :104
   const CMat Identity = CMat::identity(m);       // :106
@@ -897,7 +919,12 @@ int bcg_sbcgrq_begin(bcg_context* c, const bcg_gauge* g, double mass, bcg_field*
     return alloc_rc;
   }
   if (!consume_B) BEGIN_TRY(bcg_field_copy(st->Q, B));
-  for (int s = 0; s < n_shifts; ++s) BEGIN_TRY(bcg_field_set_zero(X[s]));  // :111-113
+  if (Y) {  // the sum of the X_s that :111-113 zero, plus c0 B -- before B can be consumed (thinQR below works on it)
+    BEGIN_TRY(bcg_field_set_zero(Y));
+    if (c0 != 0.0) BEGIN_TRY(bcg_field_add_scalar(Y, B, c0));
+  } else {
+    for (int s = 0; s < n_shifts; ++s) BEGIN_TRY(bcg_field_set_zero(X[s]));  // :111-113
+  }
   BEGIN_TRY(thin_qr(c, st->Q, st->delta));                                  // :115
   st->rho = st->delta;                                                      // :116
   for (int s = 0; s < n_shifts; ++s) BEGIN_TRY(bcg_field_copy(st->P[s], st->Q));  // :117
@@ -941,6 +968,26 @@ int bcg_sbcgrq_begin(bcg_context* c, const bcg_gauge* g, double mass, bcg_field*
   return BCG_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+int bcg_sbcgrq_begin(bcg_context* c, const bcg_gauge* g, double mass, bcg_field* const* X, bcg_field* B, int n_shifts,
+                     const double* sigma, double eps, double eps_shifts, int consume_B, bcg_sbcgrq_state** out) {
+  DeviceScope on_device(c);
+  return sbcgrq_begin(c, g, mass, X, B, n_shifts, sigma, eps, eps_shifts, consume_B, out, nullptr, nullptr, 0.0);
+}
+
+// Sum mode: the solve of bcg_sbcgrq_begin statement for statement (P_s, every coefficient, residual and the iteration count
+// bit-identical), but each X_s += P_s M becomes Y += P_s (a_s M) -- the caller keeps one field instead of n_shifts, and the
+// closing pass of a group moves one Y stream instead of the n_shifts X streams
+int bcg_sbcgrq_begin_sum(bcg_context* c, const bcg_gauge* g, double mass, bcg_field* Y, bcg_field* B, int n_shifts,
+                         const double* sigma, const double* residue, double c0, double eps, double eps_shifts, int consume_B,
+                         bcg_sbcgrq_state** out) {
+  DeviceScope on_device(c);
+  return sbcgrq_begin(c, g, mass, nullptr, B, n_shifts, sigma, eps, eps_shifts, consume_B, out, Y, residue, c0);
+}
+
 int bcg_sbcgrq_iterate(bcg_sbcgrq_state* st, int max_new_iterations, int* iterations_total, double* residual_out,
                        bcg_sbcgrq_trace* trace) {
   DeviceScope on_device(st ? st->c : nullptr);
@@ -982,6 +1029,18 @@ int bcg_sbcgrq_solve(bcg_context* c, const bcg_gauge* g, double mass, bcg_field*
   if (trace) trace->recorded = 0;
   BCG_TRY(bcg_sbcgrq_begin(c, g, mass, X, B, n_shifts, sigma, eps, eps_shifts, consume_B, &st));
   const int rc = bcg_sbcgrq_iterate(st, max_iterations, iterations_out, residual_out, trace);  // :184
+  bcg_sbcgrq_end(st);
+  return rc;
+}
+
+int bcg_sbcgrq_solve_sum(bcg_context* c, const bcg_gauge* g, double mass, bcg_field* Y, bcg_field* B, int n_shifts,
+                         const double* sigma, const double* residue, double c0, double eps, double eps_shifts, int consume_B,
+                         int max_iterations, int* iterations_out, double* residual_out, bcg_sbcgrq_trace* trace) {
+  DeviceScope on_device(c);
+  bcg_sbcgrq_state* st = nullptr;
+  if (trace) trace->recorded = 0;
+  BCG_TRY(bcg_sbcgrq_begin_sum(c, g, mass, Y, B, n_shifts, sigma, residue, c0, eps, eps_shifts, consume_B, &st));
+  const int rc = bcg_sbcgrq_iterate(st, max_iterations, iterations_out, residual_out, trace);
   bcg_sbcgrq_end(st);
   return rc;
 }

@@ -196,7 +196,12 @@ struct ShiftPtrs {
 // 32 VGPRs, the prefetch would push the kernel to one wave per SIMD, and one launch takes a single shift anyway.
 // NW: waves per block.  At m = 32 a coefficient matrix is 16.6 KB of LDS; one block of 8 waves per CU (instead of two
 // of 4) shares 9 matrices -- Rinv and four shifts -- so that 8 shifts are two launches and Q is read twice, not five times.
-template <int M, bool PREFETCH, int NW = 4>
+// SUM (sum mode, SBCGrQ_sum in capi_solvers.hip): the X_s are not touched; every shift's increment goes into ONE field
+// Y = sp.X[0] instead, Y += P_s A_s with the residue a_s already folded into A_s on the host.  Y's tile is loaded once
+// before the loop over shifts and stored once after it, its accumulator taking the shifts' products in order; P_s is
+// updated as without SUM.  (Y travels in the X slot so that the kernel's arguments, and with them the instructions of the
+// plain instantiations, stay as they are.)
+template <int M, bool PREFETCH, int NW = 4, bool SUM = false>
 __global__ void __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(1)))
 k_phaseC(int64_t rows, double2* __restrict__ Q, ShiftPtrs sp, int nshift,
                                                     const double2* __restrict__ mats, int apply_rinv) {
@@ -219,7 +224,7 @@ k_phaseC(int64_t rows, double2* __restrict__ Q, ShiftPtrs sp, int nshift,
     auto store = [&](Tile<M>& t, double2* f) __attribute__((always_inline)) { tile_store<M>(t, f, row, kq, ok); };
     Tile<M> q;
     load(q, Q);
-    Tile<M> p, x;
+    Tile<M> p, x;  // (SUM: x is Y's tile)
     if (nshift > 0) {
       load(p, sp.P[0]);
       load(x, sp.X[0]);
@@ -234,28 +239,40 @@ k_phaseC(int64_t rows, double2* __restrict__ Q, ShiftPtrs sp, int nshift,
         store(qs, Q);
       }
     }
+    Acc<M> AY;
+    if constexpr (SUM) {
+      if (nshift > 0) acc_from_tile<M>(AY, x);
+    }
     for (int s = 0; s < nshift; ++s) {
       Tile<M> pn, xn;
       if (PREFETCH && s + 1 < nshift) {  // prefetch the next shift's tiles while this one computes
         load(pn, sp.P[s + 1]);
-        load(xn, sp.X[s + 1]);
+        if constexpr (!SUM) load(xn, sp.X[s + 1]);
       }
       Acc<M> AX, AP;
-      acc_from_tile<M>(AX, x);
+      if constexpr (!SUM) acc_from_tile<M>(AX, x);
       acc_from_tile<M>(AP, q);
-      rmul_acc2<M>(AX, smat + (1 + 2 * s) * MD, AP, smat + (2 + 2 * s) * MD, p, lane);
-      tile_from_acc<M>(x, AX);
-      store(x, sp.X[s]);
+      rmul_acc2<M>(SUM ? AY : AX, smat + (1 + 2 * s) * MD, AP, smat + (2 + 2 * s) * MD, p, lane);
+      if constexpr (!SUM) {
+        tile_from_acc<M>(x, AX);
+        store(x, sp.X[s]);
+      }
       tile_from_acc<M>(p, AP);
       store(p, sp.P[s]);
       if (s + 1 < nshift) {
         if (PREFETCH) {
           p = pn;
-          x = xn;
+          if constexpr (!SUM) x = xn;
         } else {
           load(p, sp.P[s + 1]);
-          load(x, sp.X[s + 1]);
+          if constexpr (!SUM) load(x, sp.X[s + 1]);
         }
+      }
+    }
+    if constexpr (SUM) {
+      if (nshift > 0) {
+        tile_from_acc<M>(x, AY);
+        store(x, sp.X[0]);
       }
     }
   }
@@ -422,7 +439,10 @@ struct MultiSteps {
 // NORM = false (m = 32, where the residual block is stored normalised): the Q_j are used as they are and mats holds no
 // rinv_j.  PRE = false: no prefetch of the next entry's tiles (m = 32: a tile is 32 registers, and an entry's two steps
 // are 128 MFMAs per load).
-template <int M, int NW, int NS, bool NORM = true, bool PRE = true>
+// SUM (sum mode, as in k_phaseC): Y = sp.X[0]'s tile is loaded before the loop over entries and stored after it; every
+// entry's products A_ej (residues folded in on the host) and entry 0's composed X_0 matrices accumulate into one
+// accumulator, and the per-entry X loads, prefetches and stores are gone.  The P side is unchanged.
+template <int M, int NW, int NS, bool NORM = true, bool PRE = true, bool SUM = false>
 __global__ void __launch_bounds__(NW * 64)
 k_phaseC_multi(int64_t rows, MultiQ qs, ShiftPtrs sp, int nent, MultiSteps steps, int nmat, const double2* __restrict__ mats) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -437,7 +457,7 @@ k_phaseC_multi(int64_t rows, MultiQ qs, ShiftPtrs sp, int nent, MultiSteps steps
   auto body = [&](int64_t tile, auto full) __attribute__((always_inline)) {
     const int64_t row = tile * 16 + r;
     const bool ok = decltype(full)::value || BCG_ROW_OK(row, rows);
-    Tile<M> q[NS], p, x;
+    Tile<M> q[NS], p, x;  // (SUM: x is Y's tile)
 #pragma unroll
     for (int j = 0; j < NS; ++j) tile_load<M>(q[j], qs.q[j], row, kq, ok);
     if (nent > 0) {
@@ -456,21 +476,25 @@ k_phaseC_multi(int64_t rows, MultiQ qs, ShiftPtrs sp, int nent, MultiSteps steps
       }
     }
     const double* mat = smem + (NORM ? NS : 0) * MD;
+    Acc<M> AY;
+    if constexpr (SUM) {
+      if (nent > 0) acc_from_tile<M>(AY, x);
+    }
     if (NORM && steps.xacc > 0) {  // wave-uniform: the deferred X_0 updates of the group's earlier iterations
       const double* cm = mat + 2 * (steps.last[0] - steps.first[0]) * MD;
       Acc<M> AX;
-      acc_from_tile<M>(AX, x);
-      if (steps.p1 != nullptr) rmul_acc<M>(AX, p1, cm, lane);
+      if constexpr (!SUM) acc_from_tile<M>(AX, x);
+      if (steps.p1 != nullptr) rmul_acc<M>(SUM ? AY : AX, p1, cm, lane);
 #pragma unroll
       for (int j = 0; j + 1 < NS; ++j)
-        if (j + 1 < steps.xacc) rmul_acc<M>(AX, q[j], cm + (j + 1) * MD, lane);
-      tile_from_acc<M>(x, AX);
+        if (j + 1 < steps.xacc) rmul_acc<M>(SUM ? AY : AX, q[j], cm + (j + 1) * MD, lane);
+      if constexpr (!SUM) tile_from_acc<M>(x, AX);
     }
     for (int e = 0; e < nent; ++e) {
       Tile<M> pn, xn;
       if (PRE && e + 1 < nent) {  // the next entry's tiles are in flight while this one is multiplied
         tile_load<M>(pn, sp.P[e + 1], row, kq, ok);
-        tile_load<M>(xn, sp.X[e + 1], row, kq, ok);
+        if constexpr (!SUM) tile_load<M>(xn, sp.X[e + 1], row, kq, ok);
       }
       const int first = steps.first[e], last = steps.last[e];  // wave-uniform
       if (NORM && e == 1 && steps.xacc > 0) mat += steps.xacc * MD;  // entry 0's composed matrices sit behind its step matrices
@@ -478,24 +502,30 @@ k_phaseC_multi(int64_t rows, MultiQ qs, ShiftPtrs sp, int nent, MultiSteps steps
       for (int j = 0; j < NS; ++j) {
         if (j >= first && j < last) {
           Acc<M> AX, AP;
-          acc_from_tile<M>(AX, x);
+          if constexpr (!SUM) acc_from_tile<M>(AX, x);
           acc_from_tile<M>(AP, q[j]);
-          rmul_acc2<M>(AX, mat, AP, mat + MD, p, lane);
-          tile_from_acc<M>(x, AX);
+          rmul_acc2<M>(SUM ? AY : AX, mat, AP, mat + MD, p, lane);
+          if constexpr (!SUM) tile_from_acc<M>(x, AX);
           tile_from_acc<M>(p, AP);
           mat += 2 * MD;
         }
       }
-      tile_store<M>(x, sp.X[e], row, kq, ok);
+      if constexpr (!SUM) tile_store<M>(x, sp.X[e], row, kq, ok);
       tile_store<M>(p, sp.P[e], row, kq, ok);
       if (e + 1 < nent) {
         if (PRE) {
           p = pn;
-          x = xn;
+          if constexpr (!SUM) x = xn;
         } else {
           tile_load<M>(p, sp.P[e + 1], row, kq, ok);
-          tile_load<M>(x, sp.X[e + 1], row, kq, ok);
+          if constexpr (!SUM) tile_load<M>(x, sp.X[e + 1], row, kq, ok);
         }
+      }
+    }
+    if constexpr (SUM) {
+      if (nent > 0) {
+        tile_from_acc<M>(x, AY);
+        tile_store<M>(x, sp.X[0], row, kq, ok);
       }
     }
   };
@@ -757,37 +787,51 @@ int launch_phaseB(hipStream_t s, int m, int64_t rows, double2* Q, const double2*
 }
 
 void launch_phaseC(hipStream_t s, int m, int64_t rows, double2* Q, double2* const* X, double2* const* P, int nshift,
-                   const double2* mats, int apply_rinv, int max_blocks) {
+                   const double2* mats, int apply_rinv, int max_blocks, double2* Y) {
   ShiftPtrs sp{};
   for (int k = 0; k < nshift && k < 8; ++k) {
-    sp.X[k] = X[k];
+    sp.X[k] = Y ? (k == 0 ? Y : nullptr) : X[k];
     sp.P[k] = P[k];
   }
   const int grid = grid_tiles((rows + 15) / 16, 4, max_blocks);
   const int nmat = 1 + 2 * nshift - (apply_rinv ? 0 : 1);
+  // Y != nullptr: sum mode, the SUM form of the same configuration (Y in the slot of X[0])
+#define BCG_PHASEC(MM, PF, NWV, GRID)                                                                                       \
+  {                                                                                                                         \
+    if (Y) {                                                                                                                \
+      allow_lds(k_phaseC<MM, PF, NWV, true>, lds);                                                                            \
+      hipLaunchKernelGGL((k_phaseC<MM, PF, NWV, true>), dim3(GRID), dim3(NWV * 64), lds, s, rows, Q, sp, nshift, mats, apply_rinv); \
+    } else {                                                                                                                \
+      allow_lds(k_phaseC<MM, PF, NWV>, lds);                                                                                \
+      hipLaunchKernelGGL((k_phaseC<MM, PF, NWV>), dim3(GRID), dim3(NWV * 64), lds, s, rows, Q, sp, nshift, mats, apply_rinv); \
+    }                                                                                                                       \
+  }
   if (m == 8) {
     constexpr int M = 8;
     const size_t lds = sizeof(double) * ((MatLds<M>::DOUBLES + 1) & ~1) * nmat;
-    hipLaunchKernelGGL((k_phaseC<M, true>), dim3(grid), dim3(256), lds, s, rows, Q, sp, nshift, mats, apply_rinv);
+    if (Y) {
+      hipLaunchKernelGGL((k_phaseC<M, true, 4, true>), dim3(grid), dim3(256), lds, s, rows, Q, sp, nshift, mats, apply_rinv);
+    } else {
+      hipLaunchKernelGGL((k_phaseC<M, true>), dim3(grid), dim3(256), lds, s, rows, Q, sp, nshift, mats, apply_rinv);
+    }
   } else if (m == 16) {
     constexpr int M = 16;
     // (contiguous tile moves through a per-wave LDS buffer -- round 3's BCG_PHASEC_LIN -- and through the matrix pipe -- round 5,
     //  profiles/r05_phaseC_p0.txt -- measured no gain in the row kernels and are gone: the access shape does not bound them)
     const size_t lds = sizeof(double) * ((MatLds<M>::DOUBLES + 1) & ~1) * nmat;
-    allow_lds(k_phaseC<M, true>, lds);
-    hipLaunchKernelGGL((k_phaseC<M, true>), dim3(grid), dim3(256), lds, s, rows, Q, sp, nshift, mats, apply_rinv);
+    BCG_PHASEC(16, true, 4, grid)
   } else {
     constexpr int M = 32;
     const size_t lds = sizeof(double) * ((MatLds<M>::DOUBLES + 1) & ~1) * nmat;
     if (nmat > 4) {  // more matrices than two 4-wave blocks per CU can hold: one 8-wave block per CU
       const int grid8 = grid_tiles((rows + 15) / 16, 8, max_blocks / 4 > 0 ? max_blocks / 4 : 1);  // one resident block per CU
-      allow_lds(k_phaseC<M, true, 8>, lds);  // 2 waves per SIMD whatever the registers (LDS-bound): room for the tile prefetch
-      hipLaunchKernelGGL((k_phaseC<M, true, 8>), dim3(grid8), dim3(512), lds, s, rows, Q, sp, nshift, mats, apply_rinv);
+      // 2 waves per SIMD whatever the registers (LDS-bound): room for the tile prefetch
+      BCG_PHASEC(32, true, 8, grid8)
     } else {
-      allow_lds(k_phaseC<M, false>, lds);
-      hipLaunchKernelGGL((k_phaseC<M, false>), dim3(grid), dim3(256), lds, s, rows, Q, sp, nshift, mats, apply_rinv);
+      BCG_PHASEC(32, false, 4, grid)
     }
   }
+#undef BCG_PHASEC
 }
 
 void launch_phaseC_p0(hipStream_t s, int m, int64_t rows, const double2* Q, const double2* P, double2* Pout, const double2* mats,
@@ -832,12 +876,12 @@ int phaseC_multi_capacity(int m) { return static_cast<int>(150 * 1024 / mat_lds_
 
 void launch_phaseC_multi(hipStream_t s, int m, int64_t rows, int nsteps, const double2* const* Q, double2* const* X,
                          double2* const* P, int nent, const int* first, const int* last, const double2* mats, int max_blocks,
-                         bool normalise, int xacc, const double2* p1) {
+                         bool normalise, int xacc, const double2* p1, double2* Y) {
   ShiftPtrs sp{};
   MultiSteps st{};
   MultiQ qs{};
   for (int k = 0; k < nent && k < 8; ++k) {
-    sp.X[k] = X[k];
+    sp.X[k] = Y ? (k == 0 ? Y : nullptr) : X[k];
     sp.P[k] = P[k];
     st.first[k] = first[k];
     st.last[k] = last[k];
@@ -847,12 +891,18 @@ void launch_phaseC_multi(hipStream_t s, int m, int64_t rows, int nsteps, const d
   st.p1 = p1;
   const int nmat = phaseC_multi_matrices(nsteps, nent, first, last, normalise) + st.xacc;
   const int cus = max_blocks / 4 > 0 ? max_blocks / 4 : 1;  // one block per CU
+  // Y != nullptr: sum mode, the SUM form of the same configuration (Y in the slot of X[0])
 #define BCG_MULTI(MM, NW, NS, NORM, PRE)                                                                           \
   {                                                                                                                \
     const size_t lds = mat_lds_bytes(MM) * nmat;                                                                   \
     const int grid = grid_tiles((rows + 15) / 16, NW, cus);                                                        \
-    allow_lds(k_phaseC_multi<MM, NW, NS, NORM, PRE>, lds);                                                         \
-    hipLaunchKernelGGL((k_phaseC_multi<MM, NW, NS, NORM, PRE>), dim3(grid), dim3(NW * 64), lds, s, rows, qs, sp, nent, st, nmat, mats);  \
+    if (Y) {                                                                                                       \
+      allow_lds(k_phaseC_multi<MM, NW, NS, NORM, PRE, true>, lds);                                                   \
+      hipLaunchKernelGGL((k_phaseC_multi<MM, NW, NS, NORM, PRE, true>), dim3(grid), dim3(NW * 64), lds, s, rows, qs, sp, nent, st, nmat, mats); \
+    } else {                                                                                                       \
+      allow_lds(k_phaseC_multi<MM, NW, NS, NORM, PRE>, lds);                                                       \
+      hipLaunchKernelGGL((k_phaseC_multi<MM, NW, NS, NORM, PRE>), dim3(grid), dim3(NW * 64), lds, s, rows, qs, sp, nent, st, nmat, mats);  \
+    }                                                                                                              \
   }
   if (m == 8) {
     if (nsteps == 2) BCG_MULTI(8, 12, 2, true, true) else if (nsteps == 3) BCG_MULTI(8, 12, 3, true, true) else BCG_MULTI(8, 12, 4, true, true)

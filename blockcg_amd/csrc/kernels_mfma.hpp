@@ -26,8 +26,9 @@ int launch_phaseB(hipStream_t s, int m, int64_t rows, double2* Q, const double2*
                   double2* Qout = nullptr);  // Qout: the new Q goes there and Q is left as it was (nullptr: in place)
 // Phase C: q = Q*mats[0] if apply_rinv (1: stored back to Q; 2: used, not stored); for k < nshift:
 // X[k] += P[k]*mats[1+2k]; P[k] <- P[k]*mats[2+2k] + q.
+// Y != nullptr (sum mode): X is not read; Y += P[k]*mats[1+2k] for every k instead, Y read and written once.
 void launch_phaseC(hipStream_t s, int m, int64_t rows, double2* Q, double2* const* X, double2* const* P, int nshift,
-                   const double2* mats, int apply_rinv, int max_blocks);
+                   const double2* mats, int apply_rinv, int max_blocks, double2* Y = nullptr);
 // Phase C of nsteps = 2 .. 4 consecutive iterations in one pass (kernels_mfma.hip: k_phaseC_multi).  Q[j]: the
 // residual block of step j -- un-normalised with normalise = true (m = 8, 16: mats starts with rinv_0 .. rinv_{nsteps-1}),
 // as stored otherwise (m = 32) -- entry e takes the steps first[e] <= j < last[e]; then per entry and step A, B.
@@ -37,9 +38,10 @@ bool phaseC_multi_fits(int m, int nsteps, int n_shifts);  // the grouping is ava
 int phaseC_multi_capacity(int m);
 // xacc > 0 (normalise only; deferred update of X_0): before entry 0's steps, X[0] += p1 C_0 + q_0 C_1 + ... + q_{xacc-2} C_{xacc-1},
 // the xacc composed matrices following entry 0's step matrices in `mats`
+// Y != nullptr (sum mode): X is not read; every entry's X updates (and the xacc terms) go into Y, read and written once.
 void launch_phaseC_multi(hipStream_t s, int m, int64_t rows, int nsteps, const double2* const* Q, double2* const* X,
                          double2* const* P, int nent, const int* first, const int* last, const double2* mats, int max_blocks,
-                         bool normalise = true, int xacc = 0, const double2* p1 = nullptr);
+                         bool normalise = true, int xacc = 0, const double2* p1 = nullptr, double2* Y = nullptr);
 // Shift 0's phase C with the update of X_0 deferred (m = 8, 16): Pout = P mats[1] + Q mats[0]; mats = [rinv, B]
 void launch_phaseC_p0(hipStream_t s, int m, int64_t rows, const double2* Q, const double2* P, double2* Pout, const double2* mats,
                       int max_blocks);

@@ -66,6 +66,23 @@ std::pair<int, int> SBCGrQ_half_volume(std::vector<block_fermion_field<N_rhs>>& 
   }
   return std::make_pair(its[0], its[1]);
 }
+// Sum mode: Y = c0 B + sum_s residues[s] X_s, the X_s being the solutions SBCGrQ would return -- the partial-fraction form
+// of a rational function of the operator (RHMC).  The solve is SBCGrQ's, but the shifted solutions are summed into Y as
+// they are updated and never kept: one field instead of sigma.size().  Returns the operator applications.
+template <int N_rhs>
+int SBCGrQ_sum(block_fermion_field<N_rhs>& Y, const block_fermion_field<N_rhs>& B, const dirac_op& D,
+               const std::vector<double>& sigma, const std::vector<double>& residues, double c0 = 0.0, double eps = 1.e-15,
+               double eps_shifts = 1.e-15, int max_iterations = 1e6) {
+  if (residues.size() != sigma.size()) throw std::invalid_argument("number of residues does not match number of shifts");
+  B.flush();
+  int iterations = 0;
+  check(bcg_sbcgrq_solve_sum(D.lat().ctx(), D.handle(), D.mass, Y.handle(), B.handle(), static_cast<int>(sigma.size()),
+                             sigma.data(), residues.data(), c0, eps, eps_shifts, /*consume_B=*/0, max_iterations, &iterations,
+                             nullptr, nullptr),
+        D.lat().ctx(), "SBCGrQ_sum");
+  Y.device_written();
+  return iterations;
+}
 }  // namespace blockcg
 
 // BCG inversion of D X = B (inc/block_solvers.hpp:10-12); returns the number of operator applications

@@ -249,6 +249,22 @@ int bcg_sbcgrq_iterate(bcg_sbcgrq_state* state, int max_new_iterations, int* ite
                        bcg_sbcgrq_trace* trace);
 int bcg_sbcgrq_end(bcg_sbcgrq_state* state);
 
+/* Sum mode, for rational functions of the operator in partial fractions (RHMC):
+ *   Y = c0 B + sum_s residue[s] X_s,  X_s the solutions bcg_sbcgrq_solve would return (the solve is otherwise
+ * bcg_sbcgrq_solve's, statement for statement: P_s, every coefficient, residual and the iteration count are bit-identical).
+ * The X_s are never formed: each update X_s += P_s M becomes Y += P_s (residue[s] M), so the caller keeps one field
+ * instead of n_shifts.  Y: a field of B's width and parity, distinct from B; Y = c0 B is written in begin, before B can
+ * be consumed.  residue: n_shifts real, finite values; c0 finite (else BCG_ERR_INVALID).  A shift retired by eps_shifts
+ * stops contributing, exactly as its X_s stops changing; after an error Y holds c0 B + sum_s residue[s] X_s of the last
+ * completed iteration.  bcg_sbcgrq_iterate and bcg_sbcgrq_end work unchanged on the state. */
+int bcg_sbcgrq_begin_sum(bcg_context* ctx, const bcg_gauge* g, double mass, bcg_field* Y, bcg_field* B, int n_shifts,
+                         const double* sigma, const double* residue, double c0, double eps, double eps_shifts,
+                         int consume_B, bcg_sbcgrq_state** state);
+int bcg_sbcgrq_solve_sum(bcg_context* ctx, const bcg_gauge* g, double mass, bcg_field* Y, bcg_field* B, int n_shifts,
+                         const double* sigma, const double* residue, double c0, double eps, double eps_shifts,
+                         int consume_B, int max_iterations, int* iterations_out, double* residual_out,
+                         bcg_sbcgrq_trace* trace);
+
 /* ---- the callers either side of the hot path, on the same kernels ---------- */
 /* True relative residuals as the reference's tests and benchmark measure them (test/solvers.cpp:104-116,
  * benchmark.cpp:93-103): res_out[s*m + i] = |(A + sigma_s) X_s - B|_i / |B|_i. */
