@@ -6,4 +6,5 @@ drop-in headers live in blockcg_amd/include/blockcg/.
 """
 from ._lib import build, load, LIB_PATH  # noqa: F401
 from .api import (BlockCGError, Context, block_fermion_field, dirac_op, SBCGrQ, SBCGrQState, SUPPORTED_WIDTHS, true_residuals,
-                  CG, SCG, BCG, BCGrQ, SBCGrQ_half_volume, SBCGrQ_sum, SBCGrQSumState)  # noqa: F401
+                  CG, SCG, BCG, BCGrQ, SBCGrQ_half_volume, SBCGrQ_sum, SBCGrQSumState,
+                  gauge_field, fermion_force)  # noqa: F401

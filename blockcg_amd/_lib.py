@@ -114,6 +114,11 @@ SIGNATURES = {
     "bcg_bcgrq_solve": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_double, ctypes.c_int, c_int_p]),
     "bcg_sbcgrq_bytes_per_iteration": (ctypes.c_double, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
+    "bcg_force_accumulate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,
+                                            c_dbl_p, ctypes.c_double, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,
+                                            ctypes.c_void_p]),
+    "bcg_gauge_download": (ctypes.c_int, [ctypes.c_void_p, c_dbl_p]),
+    "bcg_gauge_set_zero": (ctypes.c_int, [ctypes.c_void_p]),
 }
 
 _lib = None

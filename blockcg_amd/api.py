@@ -309,6 +309,67 @@ class dirac_op:
             self.ctx.check(self.ctx.lib.bcg_dirac_hop(self.ctx.h, self.h, lhs.h, rhs.h))
 
 
+class gauge_field:
+    """A link-shaped device field of the context: one 3 x 3 complex matrix per local site and direction, host arrays
+    [V, ndim, 3, 3] in the layout dirac_op.set_links takes ([.., k, r] = M(r, k)).  fermion_force accumulates into one."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.V = ctx.V
+        self.shape = (ctx.V, ctx.ndim, 3, 3)
+        h = ctypes.c_void_p()
+        ctx.check(ctx.lib.bcg_gauge_create(ctx.h, ctypes.byref(h)))
+        self.h = h
+
+    def __del__(self):
+        try:
+            if self.h and self.ctx.h:
+                self.ctx.lib.bcg_gauge_destroy(self.h)
+            self.h = None
+        except Exception:
+            pass
+
+    def setZero(self):
+        self.ctx.check(self.ctx.lib.bcg_gauge_set_zero(self.h))
+        return self
+
+    def setRandom(self, seed=1):
+        """i.i.d. uniform [-1,1) per real component (the generator of dirac_op(ctx, seed=...))"""
+        self.ctx.check(self.ctx.lib.bcg_gauge_fill_random(self.h, seed))
+        return self
+
+    def upload(self, U):
+        a = np.ascontiguousarray(U, dtype=np.complex128)
+        if a.shape != self.shape:
+            raise ValueError(f"expected an array of shape {self.shape}, got {a.shape}")
+        self.ctx.check(self.ctx.lib.bcg_gauge_upload(self.h, _dp(a)))
+        return self
+
+    def download(self):
+        a = np.empty(self.shape, dtype=np.complex128)
+        self.ctx.check(self.ctx.lib.bcg_gauge_download(self.h, _dp(a)))
+        return a
+
+
+def fermion_force(F, X, D, residues, scale=1.0, project=False, work=None):
+    """F += scale * sum_s residues[s] G(X_s), or TA(U G) per link with project=True (include/blockcg_hip.h,
+    bcg_force_accumulate): the derivative of S = sum_s a_s B^dagger (A + sigma_s)^-1 B with respect to the links, from the
+    shifted solutions X_s.  F: a gauge_field; X: fields of one width and parity; D: the dirac_op whose links are used.
+    work: fields of X's width and parity for D X_s (None: the library allocates one); up to len(X) of them let several
+    shifts share one pass over F."""
+    ctx = D.ctx
+    S = len(X)
+    a = np.ascontiguousarray(residues, dtype=np.float64)
+    if a.shape != (S,):
+        raise ValueError("one residue per field X_s is needed")
+    Xh = (ctypes.c_void_p * S)(*[x.h for x in X])
+    work = list(work or [])
+    Wh = (ctypes.c_void_p * max(1, len(work)))(*[w.h for w in work])
+    ctx.check(ctx.lib.bcg_force_accumulate(ctx.h, D.h, Xh, S, _dp(a), float(scale), 1 if project else 0,
+                                           Wh if work else None, len(work), F.h))
+    return F
+
+
 def _trace_buffers(trace_limit, S, m):
     if trace_limit <= 0:
         return None, None, None

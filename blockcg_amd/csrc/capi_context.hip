@@ -282,6 +282,38 @@ int axpby(bcg_context* c, bcg_field* y, double a, const bcg_field* x, double b, 
   return check_launch(c, name);
 }
 
+// On a lattice divided over ranks: the ranks agree on the outcome of an allocation stretch before their first collective or
+// exchange (an all-reduce of the number of ranks that failed), so that a rank that ran out of memory does not leave its
+// peers waiting for it.  Returns alloc_rc, or BCG_ERR_HIP when another rank failed (or BCG_ERR_COMM / _HIP when the
+// all-reduce itself did).  who / what name the caller and what it allocated, for bcg_last_error.
+int agree_on_allocation(bcg_context* c, int alloc_rc, const char* who, const char* what) {
+  if (!(c->distributed && c->have_comm && c->comm.allreduce_sum)) return alloc_rc;
+  const std::string why = c->err;
+  (void)hipGetLastError();
+  if (!c->dev_gram || !c->pin_gram) (void)ensure_scratch(c);
+  double failed_ranks = alloc_rc == BCG_OK ? 0.0 : 1.0;
+  int rc_ = (c->dev_gram && c->pin_gram) ? BCG_OK : BCG_ERR_HIP;
+  if (rc_ == BCG_OK) {
+    *reinterpret_cast<double*>(c->pin_gram) = failed_ranks;
+    if (hipMemcpyAsync(c->dev_gram, c->pin_gram, sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess) rc_ = BCG_ERR_HIP;
+  }
+  if (rc_ == BCG_OK && c->comm.allreduce_sum(c->comm.user, c->dev_gram, 1) != 0) rc_ = BCG_ERR_COMM;
+  if (rc_ == BCG_OK && (hipMemcpyAsync(c->pin_gram, c->dev_gram, sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+                        hipStreamSynchronize(c->stream) != hipSuccess))
+    rc_ = BCG_ERR_HIP;
+  if (rc_ == BCG_OK) failed_ranks = *reinterpret_cast<const double*>(c->pin_gram);
+  if (alloc_rc == BCG_OK && rc_ != BCG_OK) {
+    alloc_rc = rc_;
+    c->err = std::string(who) + ": the ranks could not agree on the outcome of their allocations (all-reduce failed)";
+  } else if (alloc_rc == BCG_OK && failed_ranks > 0.0) {
+    alloc_rc = BCG_ERR_HIP;
+    c->err = std::string(who) + ": another rank of the process grid could not allocate " + what + " (hipErrorOutOfMemory there)";
+  } else {
+    c->err = why;
+  }
+  return alloc_rc;
+}
+
 // a new field of the width, parity and site count of `like`
 int create_like(bcg_context* c, const bcg_field* like, bcg_field** out) {
   return like->parity >= 0 ? bcg_field_create_half(c, like->m, like->parity, out) : bcg_field_create(c, like->m, out);

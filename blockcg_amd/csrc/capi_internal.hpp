@@ -2,6 +2,7 @@
 //   capi_context.hip    context, scratch and profiling, host <-> device transfers, field primitives, memory planning
 //   capi_operator.hip   halo exchange, the stencil launches, dirac_op::op (whole tmp, capacity ring, half-volume), gauge API
 //   capi_solvers.hip    SBCGrQ (phases A / B / C, grouped and deferred updates), CG, SCG, BCG, BCGrQ, true residuals
+//   capi_force.hip      the fermion force of multi-shift solutions (bcg_force_accumulate), gauge-field download / zero
 // Host code only; every loop over lattice sites is a HIP kernel (kernels_generic.hip, kernels_mfma.hip, kernels_stencil.hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -146,6 +147,8 @@ int rmul(bcg_context* c, bcg_field* y, const bcg_field* x, const CMat& M, double
 int trisolve(bcg_context* c, bcg_field* y, const CMat& R);
 int axpby(bcg_context* c, bcg_field* y, double a, const bcg_field* x, double b, const char* name);
 int create_like(bcg_context* c, const bcg_field* like, bcg_field** out);  // a new field of the width, parity and site count of `like`
+// divided lattice: all-reduce whether any rank failed its allocations (alloc_rc != BCG_OK) before the first exchange
+int agree_on_allocation(bcg_context* c, int alloc_rc, const char* who, const char* what);
 
 // ---- capi_operator.hip -----------------------------------------------------------------------------
 int halo_plan(int ndim, const int* gdims, const int* grid, const int* coords, size_t site_bytes, int* peer_s, int* peer_r,
@@ -154,6 +157,7 @@ inline bool can_overlap(const bcg_context* c) {
   return c->distributed && c->have_comm && c->comm.halo_exchange_begin && c->comm.halo_exchange_end;
 }
 int halo_field(bcg_context* c, const bcg_field* f, bool split = false);
+int halo_gauge(bcg_context* c, bcg_gauge* g);  // the gauge ghost (minus faces of U_mu), once per upload
 // out = D in (HOP_PLAIN) or c0 * p - D in (HOP_SHIFTED); gram_blocks: also block partials of p^dagger out in c->partials
 int hop(bcg_context* c, const bcg_gauge* g, bcg_field* out, const bcg_field* in, bcg::HopMode mode, const bcg_field* p, double c0,
         int* gram_blocks = nullptr, bool* gram_folded = nullptr);

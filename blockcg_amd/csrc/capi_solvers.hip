@@ -891,28 +891,7 @@ int sbcgrq_begin(bcg_context* c, const bcg_gauge* g, double mass, bcg_field* con
   }
   for (int s = 0; s < n_shifts && alloc_rc == BCG_OK; ++s) alloc_rc = create_like(c, B, &st->P[s]);
   if (alloc_rc == BCG_OK) alloc_rc = reserve_operator_scratch(c, B);
-  if (c->distributed && c->have_comm && c->comm.allreduce_sum) {
-    const std::string why = c->err;
-    (void)hipGetLastError();
-    double failed_ranks = alloc_rc == BCG_OK ? 0.0 : 1.0;
-    int rc_ = BCG_OK;
-    *reinterpret_cast<double*>(c->pin_gram) = failed_ranks;
-    if (hipMemcpyAsync(c->dev_gram, c->pin_gram, sizeof(double), hipMemcpyHostToDevice, c->stream) != hipSuccess) rc_ = BCG_ERR_HIP;
-    if (rc_ == BCG_OK && c->comm.allreduce_sum(c->comm.user, c->dev_gram, 1) != 0) rc_ = BCG_ERR_COMM;
-    if (rc_ == BCG_OK && (hipMemcpyAsync(c->pin_gram, c->dev_gram, sizeof(double), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-                          hipStreamSynchronize(c->stream) != hipSuccess))
-      rc_ = BCG_ERR_HIP;
-    if (rc_ == BCG_OK) failed_ranks = *reinterpret_cast<const double*>(c->pin_gram);
-    if (alloc_rc == BCG_OK && rc_ != BCG_OK) {
-      alloc_rc = rc_;
-      c->err = "SBCGrQ: the ranks could not agree on the outcome of their allocations (all-reduce failed)";
-    } else if (alloc_rc == BCG_OK && failed_ranks > 0.0) {
-      alloc_rc = BCG_ERR_HIP;
-      c->err = "SBCGrQ: another rank of the process grid could not allocate the solve's fields (hipErrorOutOfMemory there)";
-    } else {
-      c->err = why;
-    }
-  }
+  alloc_rc = agree_on_allocation(c, alloc_rc, "SBCGrQ", "the solve's fields");
   if (alloc_rc != BCG_OK) {
     sbcgrq_release(st);
     delete st;

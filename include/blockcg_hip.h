@@ -285,6 +285,34 @@ int bcg_bcgrq_solve(bcg_context* ctx, const bcg_gauge* g, double mass, bcg_field
  *   V_local * [ (14 + 4*(S-1)) * 48*m + 2 * 144*ndim ] */
 double bcg_sbcgrq_bytes_per_iteration(const bcg_context* ctx, int m, int n_shifts);
 
+/* ---- fermion force of multi-shift solutions (the molecular-dynamics force of an RHMC-type integrator) ----------------
+ * For a block pseudofermion B (m columns) under A = mass^2 - D^2 (bcg_dirac_apply) the action of a rational approximation is
+ *   S(U) = sum_s a_s sum_j B_j^dagger (A + sigma_s)^-1 B_j,      X_s = (A + sigma_s)^-1 B   (what bcg_sbcgrq_solve returns).
+ * D is anti-Hermitian for any links, so for an arbitrary complex perturbation dU of the links
+ *   dS = sum_{x,mu} Re tr( dU_mu(x) G_mu(x) ),
+ *   G_mu(x) = sum_s a_s eta_mu(x) sum_j [ Y_sj(x+mu) X_sj(x)^dagger - X_sj(x+mu) Y_sj(x)^dagger ],   Y_s = D X_s,
+ * eta_mu as for the operator above (global coordinates), x+mu periodic; each bracket is a 3 x 3 colour outer product summed
+ * over the block columns j.  (dS = sum_s a_s 2 Re X_s^dagger dD Y_s; the 1/2 of D cancels the 2.)  For an integrator that
+ * moves U -> exp(eps P) U with P traceless anti-Hermitian,
+ *   dS/deps = sum Re tr( P TA(U_mu(x) G_mu(x)) ),   TA(M) = (M - M^dagger)/2 - tr(M - M^dagger)/6 * 1.
+ *
+ * bcg_force_accumulate:  F += scale * sum_s residue[s] * G_s    (project = 0)
+ *                        F += TA(U * scale * sum_s residue[s] * G_s)   (project != 0)
+ * with residue[s] in the place of a_s.  F is a bcg_gauge of the same context used as a link-shaped container: layout
+ * [site][mu < ndim][3x3 column-major], every local site (that of bcg_gauge_upload); its contents are added to, and its gauge
+ * ghost is marked stale.  X[n_shifts]: any fields (solutions or not) of one width and one parity.  Half fields (parity p):
+ * Y_s = bcg_dirac_hop_half(X_s) has parity 1 - p and every link joins one site of each parity, so F gets entries at every
+ * site.  work[n_work]: fields of X's width and parity, the storage of Y_s (none may be an X_s); with n_work = 0 the library
+ * allocates one for the call (BCG_ERR_HIP with F untouched if it cannot); with more, up to min(n_work, n_shifts, 8) shifts
+ * share one pass over F.  Results do not depend on n_work beyond rounding.  A lattice divided over ranks exchanges the faces
+ * of X_s and Y_s (blocking); arguments are checked and memory allocated before the first exchange.
+ * BCG_ERR_INVALID: F == U; F, U or an X_s of another context; mixed widths or parities; n_shifts < 1; a non-finite residue
+ * or scale; a work field of the wrong width or parity, listed twice, or one of the X_s. */
+int bcg_force_accumulate(bcg_context* ctx, const bcg_gauge* U, bcg_field* const* X, int n_shifts, const double* residue,
+                         double scale, int project, bcg_field* const* work, int n_work, bcg_gauge* F);
+int bcg_gauge_download(const bcg_gauge* g, double* host); /* inverse of bcg_gauge_upload */
+int bcg_gauge_set_zero(bcg_gauge* g);
+
 #ifdef __cplusplus
 }
 #endif
