@@ -118,6 +118,8 @@ bool x0_may_wait(const bcg_context* c, int m) {
 int pair_shifts_depth(const bcg_context* c, int m, int n_shifts) {
   if (c->pair_shifts < 2 || !fast_rows(c, m) || !fast_rmul(c, m)) return 1;
   if (!lazy_q_width(c, m) && m != 32) return 1;  // m = 8, 16 group the un-normalised blocks; m = 32 the stored ones, in pairs
+  // m = 32 has no normalising instantiation of k_phaseC_multi: with Q left un-normalised (BCG_LAZY_Q=2) it does not group
+  if (m == 32 && lazy_q_width(c, m)) return 1;
   int d = std::min(c->pair_shifts, capacity_path(c, m) ? 2 : 4);
   while (d >= 2 && !bcg::phaseC_multi_fits(m, d, n_shifts)) --d;
   if (n_shifts < 2 && (d < 3 || !x0_may_wait(c, m))) return 1;
