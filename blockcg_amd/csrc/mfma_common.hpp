@@ -118,12 +118,57 @@ __device__ __forceinline__ void tile_from_acc(Tile<M>& t, const Acc<M>& A) {
 // acc += in * C   (C staged in LDS at Ml).  For M >= 16 the re/im block of an output tile is the same for all
 // lanes, so the choice between Re C and Im C and the sign are compile-time (the minus is the MFMA's NEG modifier).
 // For M = 8 one 16 x 16 tile holds both blocks: the A-operand lane picks its coefficient by its own output slot.
+//
+// Three real products instead of four (Gauss) where kGauss3M<M>: with x = in, c = Re C, d = Im C,
+//   K = (x_re + x_im) c ,  out_re = acc_re - x_im (c + d) + K ,  out_im = acc_im + x_re (d - c) + K.
+// The re and im accumulators run their chains from acc, K from zero; K is added at the end of the same call.  Every
+// rounding of a call depends on (acc, in, C) only, and rmul_acc2 runs this chain for each of its accumulators, so the
+// bit-identities between the fused kernels and the plain ones hold as in the four-product form.  The sums c + d, d - c
+// and x_re + x_im are formed per k-step from the values the lane reads anyway (the LDS layout is the same).
+// M = 8: one 16 x 16 tile holds both blocks and three products save nothing.  M = 32: not switched (kept at four
+// products).  -DBCG_COMPLEX_4M builds the four-product form everywhere (A/B builds).
+#ifdef BCG_COMPLEX_4M
+template <int M>
+constexpr bool kGauss3M = false;
+#else
+template <int M>
+constexpr bool kGauss3M = M == 16;
+#endif
+
+// The end of a Gauss product: K added to the re block (AR) and the im block (AI) of one output half.
+__device__ __forceinline__ void rmul_gauss_fold(d4& AR, d4& AI, const d4& K) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    AR[i] += K[i];
+    AI[i] += K[i];
+  }
+}
+
 template <int M>
 __device__ __forceinline__ void rmul_acc(Acc<M>& A, const Tile<M>& in, const double* Ml, int lane) {
   static_assert(M == 8 || M == 16 || M == 32, "MFMA right-multiply is instantiated for m = 8, 16, 32");
   constexpr int LD = MatLds<M>::LD;
   const int kq = lane >> 4;          // which of the 4 k-slots of a step this lane feeds (B operand)
   const int ar = lane & 15;          // A-operand row: output slot dr = kq_o + 4*reg_o
+  if constexpr (kGauss3M<M>) {
+    constexpr int H = M / 16;        // output halves: A.a[h] is the re block of half h, A.a[H + h] its im block
+#pragma unroll
+    for (int h = 0; h < H; ++h) {
+      const int j_o = 4 * (4 * h + (ar >> 2)) + (ar & 3);
+      const double* base = Ml + kq * LD + 2 * j_o;
+      d4 K = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int s_i = 0; s_i < M / 4; ++s_i) {
+        const double c = base[s_i * 4 * LD + 0];                 // Re C(j_i, j_o)
+        const double d = base[s_i * 4 * LD + 1];                 // Im C(j_i, j_o)
+        K = mfma(c, in.v[s_i].x + in.v[s_i].y, K);
+        A.a[h] = mfma_nega(c + d, in.v[s_i].y, A.a[h]);
+        A.a[H + h] = mfma(d - c, in.v[s_i].x, A.a[H + h]);
+      }
+      rmul_gauss_fold(A.a[h], A.a[H + h], K);
+    }
+    return;
+  }
 #pragma unroll
   for (int T = 0; T < (M + 7) / 8; ++T) {
     const int q_o = 4 * T + (ar >> 2);                           // output slot index: ri_o*(M/4) + s_o
@@ -162,6 +207,29 @@ __device__ __forceinline__ void rmul_acc2(Acc<M>& A1, const double* Ml1, Acc<M>&
   constexpr int LD = MatLds<M>::LD;
   const int kq = lane >> 4;
   const int ar = lane & 15;
+  if constexpr (kGauss3M<M>) {  // rmul_acc's chain for each accumulator; the B operands and x_re + x_im are shared
+    constexpr int H = M / 16;
+#pragma unroll
+    for (int h = 0; h < H; ++h) {
+      const int off = kq * LD + 2 * (4 * (4 * h + (ar >> 2)) + (ar & 3));
+      d4 K1 = d4{0.0, 0.0, 0.0, 0.0}, K2 = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int s_i = 0; s_i < M / 4; ++s_i) {
+        const double c1 = Ml1[off + s_i * 4 * LD], d1 = Ml1[off + s_i * 4 * LD + 1];
+        const double c2 = Ml2[off + s_i * 4 * LD], d2 = Ml2[off + s_i * 4 * LD + 1];
+        const double xs = in.v[s_i].x + in.v[s_i].y;
+        K1 = mfma(c1, xs, K1);
+        K2 = mfma(c2, xs, K2);
+        A1.a[h] = mfma_nega(c1 + d1, in.v[s_i].y, A1.a[h]);
+        A2.a[h] = mfma_nega(c2 + d2, in.v[s_i].y, A2.a[h]);
+        A1.a[H + h] = mfma(d1 - c1, in.v[s_i].x, A1.a[H + h]);
+        A2.a[H + h] = mfma(d2 - c2, in.v[s_i].x, A2.a[H + h]);
+      }
+      rmul_gauss_fold(A1.a[h], A1.a[H + h], K1);
+      rmul_gauss_fold(A2.a[h], A2.a[H + h], K2);
+    }
+    return;
+  }
 #pragma unroll
   for (int T = 0; T < (M + 7) / 8; ++T) {
     const int q_o = 4 * T + (ar >> 2);

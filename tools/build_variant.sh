@@ -1,13 +1,11 @@
 #!/bin/bash
 # Build a variant of the library with extra compile flags: tools/build_variant.sh <name> "<flags>"
 # -> blockcg_amd/_build/libblockcg_hip_<name>.so  (select with BCG_LIB or tools/ab_bench.sh)
+# Through the Makefile (EXTRA = the flags, OUT = a directory of the variant's own), so the variant links every object
+# of the default build and the flags reach every source file.
 set -e
 name=$1; flags=$2
 cd "$(dirname "$0")/../blockcg_amd/csrc"
-mkdir -p /tmp/bcg_variants
-# (the flags reach both kernel files: the stencil's switches live in kernels_stencil.hip, the row kernels' in kernels_mfma.hip)
-/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 $flags -c kernels_stencil.hip -o /tmp/bcg_variants/ks_$name.o &
-/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 $flags -c kernels_mfma.hip -o /tmp/bcg_variants/km_$name.o &
-wait
-/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o ../_build/libblockcg_hip_$name.so ../_build/capi_context.o ../_build/capi_operator.o ../_build/capi_solvers.o ../_build/kernels_generic.o /tmp/bcg_variants/km_$name.o /tmp/bcg_variants/ks_$name.o
+make -j16 OUT=../_build/variant_$name EXTRA="$flags" ../_build/variant_$name/libblockcg_hip.so
+cp -f ../_build/variant_$name/libblockcg_hip.so ../_build/libblockcg_hip_$name.so
 echo built $name
