@@ -119,6 +119,10 @@ SIGNATURES = {
                                             ctypes.c_void_p]),
     "bcg_gauge_download": (ctypes.c_int, [ctypes.c_void_p, c_dbl_p]),
     "bcg_gauge_set_zero": (ctypes.c_int, [ctypes.c_void_p]),
+    "bcg_field_fill_noise": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64]),
+    "bcg_field_set_point_sources": (ctypes.c_int, [ctypes.c_void_p, c_int_p, c_int_p]),
+    "bcg_field_set_wall_sources": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_int_p, c_int_p, ctypes.c_int]),
+    "bcg_field_slice_dot": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, c_dbl_p]),
 }
 
 _lib = None

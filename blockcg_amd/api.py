@@ -14,6 +14,8 @@ import numpy as np
 from . import _lib
 from ._lib import c_dbl_p
 
+NOISE_GAUSSIAN, NOISE_Z2, NOISE_Z4 = 0, 1, 2  # BCG_NOISE_* of include/blockcg_hip.h
+
 SUPPORTED_WIDTHS = tuple(range(1, 33))  # the reference's N_rhs is any int (inc/fields.hpp:19-26)
 
 _STATUS = {1: "BCG_ERR_INVALID", 2: "BCG_ERR_UNSUPPORTED", 3: "BCG_ERR_HIP", 4: "BCG_ERR_NO_DEVICE", 5: "BCG_ERR_COMM",
@@ -216,6 +218,51 @@ class block_fermion_field:
     def setRandom(self, seed=1):
         self.ctx.check(self.ctx.lib.bcg_field_fill_random(self.h, seed))
         return self
+
+    # sources and sinks on the device (include/blockcg_hip.h: noise, point / wall sources, slice sums)
+    def _fill_noise(self, kind, seed):
+        self.ctx.check(self.ctx.lib.bcg_field_fill_noise(self.h, kind, seed))
+        return self
+
+    def setGaussian(self, seed=1):
+        """Complex Gaussian noise of density exp(-|z|^2) (<|z|^2> = 1) from the generator of setRandom."""
+        return self._fill_noise(NOISE_GAUSSIAN, seed)
+
+    def setZ2(self, seed=1):
+        return self._fill_noise(NOISE_Z2, seed)
+
+    def setZ4(self, seed=1):
+        return self._fill_noise(NOISE_Z4, seed)
+
+    def setPointSources(self, coords, colours):
+        """Zero, then column j has a 1 at the GLOBAL site coords[j] (ndim entries each), colour colours[j]."""
+        m = self.N_rhs
+        xs = np.zeros((m, 4), dtype=np.intc)
+        cs = np.asarray(coords, dtype=np.intc).reshape(m, -1)
+        xs[:, :cs.shape[1]] = cs
+        col = np.ascontiguousarray(np.asarray(colours, dtype=np.intc).reshape(m))
+        self.ctx.check(self.ctx.lib.bcg_field_set_point_sources(self.h, xs.ctypes.data_as(_lib.c_int_p),
+                                                                col.ctypes.data_as(_lib.c_int_p)))
+        return self
+
+    def setWallSources(self, dir, slices, colours, parity=-1):
+        """Zero, then column j has a 1 in colour colours[j] on the sites with GLOBAL x_dir = slices[j] (parity: -1 all, 0 even,
+        1 odd sites of the slice)."""
+        m = self.N_rhs
+        sl = np.ascontiguousarray(np.asarray(slices, dtype=np.intc).reshape(m))
+        col = np.ascontiguousarray(np.asarray(colours, dtype=np.intc).reshape(m))
+        self.ctx.check(self.ctx.lib.bcg_field_set_wall_sources(self.h, int(dir), sl.ctypes.data_as(_lib.c_int_p),
+                                                               col.ctypes.data_as(_lib.c_int_p), int(parity)))
+        return self
+
+    def slice_dot(self, rhs, dir):
+        """[L_dir global, N_rhs]: sum over the sites of slice x_dir = t and the colours of conj(this) * rhs, per column;
+        summed over ranks.  Its sum over t is the diagonal of hermitian_dot(rhs)."""
+        if not 0 <= int(dir) < self.ctx.ndim:
+            raise BlockCGError(1, "slice_dot: direction outside the lattice")
+        out = np.empty((self.ctx.dims[int(dir)], self.N_rhs), dtype=np.complex128)
+        self.ctx.check(self.ctx.lib.bcg_field_slice_dot(self.h, rhs.h, int(dir), _dp(out)))
+        return out
 
     def __iadd__(self, rhs):
         self.ctx.check(self.ctx.lib.bcg_field_add_assign(self.h, rhs.h))

@@ -194,6 +194,37 @@ class block_fermion_field {
     blockcg::check(bcg_field_fill_random(f_, seed), lat_->ctx(), "setRandomDevice");
     host_valid_ = host_dirty_ = false;
   }
+  // Sources and sinks on the device (include/blockcg_hip.h; not in the reference): noise from the same counter generator,
+  // point / wall sources at GLOBAL coordinates, and the inner product resolved by slice and column.
+  void setGaussian(unsigned long long seed) { noise(BCG_NOISE_GAUSSIAN, seed); }  // density exp(-|z|^2), <|z|^2> = 1
+  void setZ2(unsigned long long seed) { noise(BCG_NOISE_Z2, seed); }
+  void setZ4(unsigned long long seed) { noise(BCG_NOISE_Z4, seed); }
+  // column j: a 1 at site coords[j] (up to 4 entries, missing ones 0), colour colours[j]; zero elsewhere
+  void setPointSources(const std::vector<std::vector<int>>& coords, const std::vector<int>& colours) {
+    if (coords.size() != static_cast<size_t>(N_rhs) || colours.size() != static_cast<size_t>(N_rhs))
+      throw std::runtime_error("setPointSources: one site and one colour per right-hand side");
+    std::vector<int> x(4 * N_rhs, 0);
+    for (int j = 0; j < N_rhs; ++j)
+      for (size_t mu = 0; mu < coords[j].size() && mu < 4; ++mu) x[4 * j + mu] = coords[j][mu];
+    blockcg::check(bcg_field_set_point_sources(f_, x.data(), colours.data()), lat_->ctx(), "setPointSources");
+    host_valid_ = host_dirty_ = false;
+  }
+  // column j: a 1 in colour colours[j] on the sites with x_dir = slices[j] (parity: -1 all, 0 even, 1 odd sites)
+  void setWallSources(int dir, const std::vector<int>& slices, const std::vector<int>& colours, int parity = -1) {
+    if (slices.size() != static_cast<size_t>(N_rhs) || colours.size() != static_cast<size_t>(N_rhs))
+      throw std::runtime_error("setWallSources: one slice and one colour per right-hand side");
+    blockcg::check(bcg_field_set_wall_sources(f_, dir, slices.data(), colours.data(), parity), lat_->ctx(), "setWallSources");
+    host_valid_ = host_dirty_ = false;
+  }
+  // [t * N_rhs + j] = sum over the sites of slice x_dir = t and the colours of conj(this) * rhs, column j; t global
+  std::vector<std::complex<double>> slice_dot(const block_fermion_field& rhs, int dir) const {
+    if (dir < 0 || dir >= static_cast<int>(lat_->dims().size())) throw std::runtime_error("slice_dot: direction outside the lattice");
+    flush();
+    rhs.flush();
+    std::vector<std::complex<double>> out(static_cast<size_t>(lat_->dims()[dir]) * N_rhs);
+    blockcg::check(bcg_field_slice_dot(f_, rhs.f_, dir, reinterpret_cast<double*>(out.data())), lat_->ctx(), "slice_dot");
+    return out;
+  }
   // this <- this + rhs * rhs_multiplier (:70-77)
   block_fermion_field& add(const block_fermion_field& rhs, double rhs_multiplier) {
     dev2(rhs);
@@ -290,6 +321,10 @@ class block_fermion_field {
       blockcg::check(bcg_field_download(f_, reinterpret_cast<double*>(host_.data())), lat_->ctx(), "download");
       host_valid_ = true;
     }
+  }
+  void noise(int kind, unsigned long long seed) {
+    blockcg::check(bcg_field_fill_noise(f_, kind, seed), lat_->ctx(), "fill_noise");
+    host_valid_ = host_dirty_ = false;
   }
   void dev1() {
     flush();

@@ -313,6 +313,36 @@ int bcg_force_accumulate(bcg_context* ctx, const bcg_gauge* U, bcg_field* const*
 int bcg_gauge_download(const bcg_gauge* g, double* host); /* inverse of bcg_gauge_upload */
 int bcg_gauge_set_zero(bcg_gauge* g);
 
+/* ---- sources and sinks on the device: noise, point / wall sources, slice sums ------------------------------------------
+ * What a solve starts from and what a measurement takes out of it, without a whole-field transfer.  Coordinates and slice
+ * indices are GLOBAL; on a lattice divided over ranks every rank makes the same call and fills or sums the sites it holds.
+ * Argument checks use global data only, so every rank returns the same status; after BCG_ERR_INVALID the field is as it was.
+ *
+ * Noise.  The counter generator of bcg_field_fill_random gives a complex element two uniforms a, b in [-1, 1) (its real
+ * and imaginary part there); from the same two, so that a value depends on seed and the GLOBAL element index only:
+ *   BCG_NOISE_GAUSSIAN  z = sqrt(-ln((1 - a) / 2)) * (cos(pi b), sin(pi b)): density exp(-|z|^2), <|z|^2> = 1, |z| <= 6.1
+ *   BCG_NOISE_Z2        z = (a < 0 ? -1 : +1, 0)
+ *   BCG_NOISE_Z4        z = ((a < 0 ? -1 : +1), (b < 0 ? -1 : +1)) / sqrt(2)
+ * Half fields get the values the full field has on their sites.  Unknown kind: BCG_ERR_INVALID. */
+#define BCG_NOISE_GAUSSIAN 0
+#define BCG_NOISE_Z2 1
+#define BCG_NOISE_Z4 2
+int bcg_field_fill_noise(bcg_field* f, int kind, uint64_t seed);
+/* f = 0, then column j has a 1 at site coords[4*j .. 4*j+3] (entries beyond ndim must be 0), colour colour[j].
+ * BCG_ERR_INVALID: a coordinate outside the global lattice, a colour outside 0..2, on a half field a site of the other parity. */
+int bcg_field_set_point_sources(bcg_field* f, const int* coords, const int* colour);
+/* f = 0, then column j has a 1 in colour colour[j] on every site with x_dir = slice[j] whose parity x_0+x_1+x_2+x_3 (mod 2)
+ * is site_parity (-1: every site of the slice).  A half field accepts -1 or its own parity.  One pass over f.
+ * BCG_ERR_INVALID as above, or dir outside 0 .. ndim-1. */
+int bcg_field_set_wall_sources(bcg_field* f, int dir, const int* slice, const int* colour, int site_parity);
+/* out[t*m + j] = sum_{x: x_dir = t} sum_c conj(a[x,c,j]) b[x,c,j], t over the GLOBAL extent of direction dir, interleaved
+ * (re, im): the diagonal of bcg_field_hermitian_dot resolved by slice.  Summed over all ranks (bcg_comm.allreduce_sum) and
+ * identical on every rank; the same bits on every call (fixed blocks per slice, block sums added in a fixed order, no
+ * atomics).  a == b reads the field once.  Half fields: both operands of one parity, the sites held contribute.
+ * BCG_ERR_INVALID: mixed widths, parities or contexts, dir outside 0 .. ndim-1; BCG_ERR_UNSUPPORTED: more than 2^20 / m
+ * slices.  Synchronizes the stream. */
+int bcg_field_slice_dot(const bcg_field* a, const bcg_field* b, int dir, double* out);
+
 #ifdef __cplusplus
 }
 #endif
