@@ -446,6 +446,9 @@ int bcg_scg_solve(bcg_context* c, const bcg_gauge* g, double mass, bcg_field* co
   BCG_TRY(real_dot(c, r, r, rr));              // :55
   int iter = 0;
   const double stop = eps * std::sqrt(rr);     // :57
+  // coefficients and field pointers of the fused update, by shift; the first `active` (>= 1) entries are used
+  std::vector<double> a_s(n_shifts), b_s(n_shifts), z_s(n_shifts);
+  std::vector<double2*> xs(n_shifts), ps(n_shifts);
   while (std::sqrt(rr) > stop && iter < max_iterations) {  // :58
     BCG_TRY(apply_shifted(c, g, mass, sigma[0], t, p[0]));  // :60-61
     ++iter;
@@ -459,8 +462,6 @@ int bcg_scg_solve(bcg_context* c, const bcg_gauge* g, double mass, bcg_field* co
     beta = rr / rr_old;                                     // :71
     // :73-87 -- the updates of all active shifts as ONE pass over r, x_s, p_s (k_scg_update; same expressions as the
     // axpys, so the same iterates): coefficients first, then one launch
-    std::vector<double> a_s(active), b_s(active), z_s(active);
-    std::vector<double2*> xs(active), ps(active);
     a_s[0] = alpha; b_s[0] = beta; z_s[0] = 1.0;            // :73, :75
     for (int s = active - 1; s > 0; --s) {                  // :76
       double inv_theta = 1.0 + (sigma[s] - sigma[0]) * alpha;              // :78
@@ -477,7 +478,10 @@ int bcg_scg_solve(bcg_context* c, const bcg_gauge* g, double mass, bcg_field* co
       bcg::launch_scg_update(c->stream, r->d, active, xs.data(), ps.data(), a_s.data(), b_s.data(), z_s.data(), rows_of(r));
     }
     BCG_TRY(check_launch(c, "scg_update"));
-    if (std::sqrt(rr) * zeta[active - 1] < eps_shifts) --active;           // :90-92
+    // :90-92.  Shift 0 never retires: the reference updates x_0, p_0 outside its shift loop (:73-75) whatever the counter
+    // says, and here shift 0 is entry 0 of the fused launch -- so the counter stops at 1 (eps_shifts is compared with the
+    // UNNORMALISED residual times zeta, eps is scaled by |b|: without the floor eps_shifts > eps |b| would retire the base)
+    if (active > 1 && std::sqrt(rr) * zeta[active - 1] < eps_shifts) --active;
   }
   BCG_TRY(stream_sync(c));
   if (iterations_out) *iterations_out = iter;

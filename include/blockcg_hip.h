@@ -270,7 +270,9 @@ int bcg_sbcgrq_solve_sum(bcg_context* ctx, const bcg_gauge* g, double mass, bcg_
  * benchmark.cpp:93-103): res_out[s*m + i] = |(A + sigma_s) X_s - B|_i / |B|_i. */
 int bcg_true_residuals(bcg_context* ctx, const bcg_gauge* g, double mass, bcg_field* const* X, const bcg_field* B,
                        int n_shifts, const double* sigma, double* res_out);
-/* CG  src/standard_solvers.cpp:3-32   and   SCG  src/standard_solvers.cpp:34-95   (fields of width 1) */
+/* CG  src/standard_solvers.cpp:3-32   and   SCG  src/standard_solvers.cpp:34-95   (fields of width 1).
+ * SCG compares eps_shifts with the UNNORMALISED residual |r| times zeta_s, as the reference does (:90), while eps is
+ * scaled by |b| (:57); the base system (shift 0) never retires and runs to eps whatever eps_shifts is. */
 int bcg_cg_solve(bcg_context* ctx, const bcg_gauge* g, double mass, bcg_field* x, const bcg_field* b, double eps,
                  int max_iterations, int* iterations_out);
 int bcg_scg_solve(bcg_context* ctx, const bcg_gauge* g, double mass, bcg_field* const* x, const bcg_field* b, int n_shifts,

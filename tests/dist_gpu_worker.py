@@ -93,10 +93,45 @@ def main():
         assert e < 1e-11, ("X", s, rank, e)
     if os.environ.get("BCG_TEST_HALF") == "1":
         half_volume_checks(ctx, comm, orc, D, B, U, Bh, gdims, mass, m, local, rel)
+    if os.environ.get("BCG_TEST_STANDARD") == "1":
+        standard_solver_checks(ctx, comm, orc, D, B, U, Bh, gdims, mass, iters, local, rel)
     dist.barrier()
     if rank == 0:
         print("DIST_GPU_OK", world, grid, "generic" if generic else "fast", "op err %.2e" % e_op)
     dist.destroy_process_group()
+
+
+def standard_solver_checks(ctx, comm, orc, D, B, U, Bh, gdims, mass, iters, local, rel):
+    """SCG and BCG on a lattice divided over ranks (tests/test_standard_solvers.py has them on one rank): the all-reduce under
+    real_dot and the Gram matrices, the halo exchange of apply_shifted.  A fixed number of iterations, this rank's sites
+    against the whole-lattice oracle."""
+    shifts = [0.0, 1e-3, 0.5]
+    V = int(np.prod(gdims))
+    bh = orc.fill_field(1, V, 8)
+    b = bc.block_fermion_field(ctx, 1).setRandom(seed=8)
+    xs = [bc.block_fermion_field(ctx, 1) for _ in shifts]
+    it = bc.SCG(xs, b, D, shifts, 0.0, 0.0, max_iterations=iters)
+    if comm.error:
+        raise comm.error
+    xo, ito = orc.scg(U, gdims, mass, bh, shifts, 0.0, 0.0, iters)
+    assert it == ito == iters
+    for s in range(len(shifts)):
+        e = rel(xs[s].download(), local_of(xo[s], gdims, ctx, 1))
+        assert e < 1e-11, ("SCG x", s, e)
+    X = bc.block_fermion_field(ctx, B.N_rhs)
+    it = bc.BCG(X, B, D, 0.0, max_iterations=iters)
+    if comm.error:
+        raise comm.error
+    Xo, ito = orc.bcg(U, gdims, mass, Bh, 0.0, iters)
+    assert it == ito == iters
+    e = rel(X.download(), local(Xo))
+    assert e < 1e-11, ("BCG X", e)
+
+
+def local_of(a, gdims, ctx, m):
+    """[V, m, 3] global -> this rank's sites in local lexicographic order (main's `local` for another width)"""
+    sl = tuple(slice(o, o + l) for o, l in zip(ctx.origin, ctx.local_dims))[::-1]
+    return np.ascontiguousarray(a.reshape(gdims[::-1] + [m, 3])[sl]).reshape(-1, m, 3)
 
 
 HALF_SHIFTS, HALF_EPS = [0.0, 1e-3, 5e-2], 1e-10

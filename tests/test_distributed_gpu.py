@@ -43,7 +43,7 @@ def _sweep_mock_files():
 
 
 def _run_ranks(dims, grid, m, generic, ring=0, blocks="8", patch="16,2,2", overlap=True, native=False, expect_ring_overlap=False,
-               half=False, expect_checkerboard=False, half_chunk=0):
+               half=False, expect_checkerboard=False, half_chunk=0, standard=False):
     world = 1
     for g in grid:
         world *= g
@@ -60,6 +60,8 @@ def _run_ranks(dims, grid, m, generic, ring=0, blocks="8", patch="16,2,2", overl
         env.update(BCG_TEST_EXPECT_CHECKERBOARD="1")
     if half_chunk:
         env.update(BCG_HALF_CHUNK=str(half_chunk), BCG_TEST_EXPECT_HALF_CHUNKED="1")
+    if standard:
+        env.update(BCG_TEST_STANDARD="1")
     port = 29700 + (hash((tuple(dims), tuple(grid), m, ring)) % 200)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "tests", "dist_gpu_worker.py")]
@@ -73,6 +75,13 @@ def _run_ranks(dims, grid, m, generic, ring=0, blocks="8", patch="16,2,2", overl
 @pytest.mark.parametrize("dims,grid,m,generic", CASES, ids=lambda v: "x".join(map(str, v)) if isinstance(v, list) else str(v))
 def test_domain_decomposed_solve(dims, grid, m, generic):
     _run_ranks(dims, grid, m, generic)
+
+
+def test_scg_and_bcg_on_a_divided_lattice():
+    """The solvers beside SBCGrQ on a lattice divided over 4 ranks, x0 and x3 (tests/dist_gpu_worker.py,
+    standard_solver_checks): SCG with 3 shifts on a width-1 field and BCG at m = 5, four fixed iterations, every rank's
+    sites against the whole-lattice oracle."""
+    _run_ranks([8, 4, 4, 8], [2, 1, 1, 2], 5, False, standard=True)
 
 
 HALF_CASES = [
