@@ -258,7 +258,7 @@ int rmul(bcg_context* c, bcg_field* y, const bcg_field* x, const CMat& M, double
   BCG_TRY(upload_mat(c, M, &Md));
   {
     ProfScope ps(c, name, alg_bytes(c, y->m, (x && x != y) ? 3 : 2));
-    if (fast_rmul(c, y->m)) bcg::launch_rmul_mfma(c->stream, y->m, rows_of(y), y->d, x ? x->d : nullptr, Md, b, mode, kFastBlocks);
+    if (fast_rmul(c, y->m)) bcg::launch_rmul_mfma(c->stream, y->m, rows_of(y), y->d, x ? x->d : nullptr, Md, b, mode, kFastBlocks, c->row_batched);
     else bcg::launch_rmul_generic(c->stream, y->m, rows_of(y), y->d, x ? x->d : nullptr, Md, b, mode);
   }
   return check_launch(c, name);
@@ -389,6 +389,7 @@ int bcg_context_create(bcg_context** out, int device, void* stream, int ndim, co
   // tuning overrides for experiments (tools/hop_sweep.py); defaults in kernels_mfma.hpp
   if (const char* e = std::getenv("BCG_ROW_BLOCKS_B")) c->row_blocks_B = std::atoi(e);
   if (const char* e = std::getenv("BCG_ROW_BLOCKS_C")) c->row_blocks_C = std::atoi(e);
+  if (const char* e = std::getenv("BCG_ROW_BATCHED")) c->row_batched = std::atoi(e) != 0;
   if (const char* e = std::getenv("BCG_HOP_WALK")) c->hop_tune.patch_walk = std::atoi(e) != 0;
   if (const char* e = std::getenv("BCG_HOP_BLOCKS")) c->hop_tune.blocks = std::atoi(e);
   if (const char* e = std::getenv("BCG_HOP_BLOCKS_OVERLAP")) c->hop_tune.blocks_overlap = std::atoi(e);

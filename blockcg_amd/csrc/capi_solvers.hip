@@ -43,7 +43,7 @@ int phase_B(bcg_context* c, bcg_field* Q, const bcg_field* T, const CMat& alpha,
   int nb;
   {
     ProfScope ps(c, "phaseB", row_bytes(Q, 3), product_flops(Q, rinv_prev ? 3 : 2));  // [rho^-1,] alpha, Gram
-    nb = bcg::launch_phaseB(c->stream, m, rows_of(Q), Q->d, T->d, Md, c->partials, c->row_blocks_B,
+    nb = bcg::launch_phaseB(c->stream, m, rows_of(Q), Q->d, T->d, Md, c->partials, c->row_blocks_B, c->row_batched,
                             bcg::GramFold{c->dev_gram, c->fold_tickets},
                             rinv_prev ? Md + static_cast<size_t>(m) * m : nullptr, Qout ? Qout->d : nullptr);
   }
@@ -718,7 +718,7 @@ int sbcgrq_iteration(bcg_sbcgrq_state* st, bcg_sbcgrq_trace* trace, bool more_fo
       bcg_field* const out = (st->pending.empty() && !x0_backward) ? st->P0_spare : st->P[0];
       {
         ProfScope ps(c, "phaseC_p0", row_bytes(st->Q, 3), product_flops(st->Q, 2));
-        bcg::launch_phaseC_p0(c->stream, m, rows_of(st->Q), st->Q->d, st->P[0]->d, out->d, Md, c->row_blocks_C);
+        bcg::launch_phaseC_p0(c->stream, m, rows_of(st->Q), st->Q->d, st->P[0]->d, out->d, Md, c->row_blocks_C, c->row_batched);
       }
       BCG_TRY(check_launch(c, "phaseC_p0"));
       if (st->pending.empty() && !x0_backward) {

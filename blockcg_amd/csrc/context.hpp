@@ -55,6 +55,7 @@ struct bcg_context {
   bool force_generic = false;
   bool force_tile_classes = false;  // tuning/test aid: interior + boundary stencil launches on an undivided lattice too
   int row_blocks_B = 1024, row_blocks_C = 1024;  // persistent grids of the fused row kernels (phase B, phase C)
+  bool row_batched = true;  // m = 16: phase B, k_phaseC_p0 and K5 / K6 batch their stores through LDS (BCG_ROW_BATCHED=0: the plain kernels)
   bcg::HopTuning hop_tune;  // specialised stencil: tile walk, patch shape, grid, streaming hints
 
   // scratch

@@ -1,5 +1,8 @@
-// MFMA fast path for gfx950 (MI355X): fused SBCGrQ phase kernels for block widths m = 16 and 32
-// (the stencil is in kernels_stencil.hip).  Wave = 64 lanes throughout; no other target is supported.
+// MFMA fast path for gfx950 (MI355X), block widths m = 8, 16 and 32: the fused SBCGrQ phase kernels (k_phaseB / k_phaseB8,
+// k_phaseC, k_phaseC_p0, k_phaseC_multi), the stand-alone right-multiplications and Gram products (k_rmul_mfma, k_gram_mfma /
+// k_gram_mfma8), and at m = 16 the forms of phase B, k_phaseC_p0 and k_rmul_mfma that batch their stores per chunk of tiles
+// through LDS (k_*_batched); with their launchers.  The stencil is in kernels_stencil.hip.  Wave = 64 lanes throughout; no
+// other target is supported.
 //
 // A block field is a tall real matrix of 3V rows x 2m columns, (re,im) interleaved, rows contiguous.
 // The tall-skinny products  out = in * C  (C complex m x m) are done by v_mfma_f64_16x16x4_f64 in
@@ -95,20 +98,30 @@ __global__ void __launch_bounds__(256) k_phaseB(int64_t rows, const double2* Q, 
   gram_fold<M * M>(gf, partials, tid, NW * 64);
 }
 
-// Phase B with its stores BATCHED (round 5; tools/microbench/rw_phased.hip, and k_phaseC_p0_batched below for the form): a
+// The chunk-staged form of the m = 16 row kernels (k_phaseB_batched, k_phaseC_p0_batched, k_rmul_mfma_batched) and their
+// launchers share these: tiles per chunk, waves per block, the stride of a staged row and the bytes of a staged chunk.
+// In place (phase B also over T, K5 / K6 on y) is safe in all three: a block has read its whole chunk of every input
+// before it writes that chunk, and no other block touches it.
+// (One device template for the walk of the three kernels was tried and is not here: DESIGN.md section 6, "One chunk walk".)
+constexpr int kChunkTiles = 32;  // (chunks of 16, two blocks per CU: no gain, profiles/r05_batched_stores.txt)
+constexpr int kChunkWaves = 8;
+constexpr int chunk_row_stride(int m) { return m + 1; }  // double2 per staged row: one element of padding against bank conflicts
+constexpr size_t chunk_stage_bytes(int m, int n) { return sizeof(double2) * n * 16 * chunk_row_stride(m); }
+
+// Phase B with its stores BATCHED (round 5; tools/microbench/rw_phased.hip): a
 // block of 8 waves owns chunks of N consecutive tiles, wave w takes tiles w, w + 8, ... of the chunk with the next one's
 // loads in flight, leaves each new tile in LDS in the field's own layout (rows padded by one element: the same buffer is
 // the transposition source of the fused Gram product), and after a barrier the block writes the chunk, contiguous.  The
-// first tiles of the block's next chunk are in flight during the stores.  In place (Qout == Q) and over T are safe: a block
-// has read its whole chunk of both before it writes.  Same products as k_phaseB; the Gram partial sums run over other
+// first tiles of the block's next chunk are in flight during the stores.  In place (Qout == Q) and over T: see above.
+// Same products as k_phaseB; the Gram partial sums run over other
 // tiles per wave and block (a different, equally valid summation order).  rows must be a multiple of 16 N.
 template <int M, int N>
-__global__ void __launch_bounds__(512) k_phaseB_batched(int64_t rows, const double2* Q, const double2* T,
+__global__ void __launch_bounds__(kChunkWaves * 64) k_phaseB_batched(int64_t rows, const double2* Q, const double2* T,
                                                         const double2* __restrict__ negalpha, double2* __restrict__ partials,
                                                         GramFold gf, const double2* __restrict__ rinv, double2* Qout) {
   static_assert(M == 16, "the batched phase B is instantiated for m = 16");
-  constexpr int NW = 8;
-  constexpr int RS = M + 1;  // double2 per staged row (= k_phaseB's transposition row, M * 2 + 2 doubles)
+  constexpr int NW = kChunkWaves;
+  constexpr int RS = chunk_row_stride(M);  // double2 per staged row (= k_phaseB's transposition row, M * 2 + 2 doubles)
   constexpr int MDs = (MatLds<M>::DOUBLES + 1) & ~1;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   double* Ml = smem;
@@ -338,15 +351,15 @@ __global__ void __launch_bounds__(256) k_phaseC_p0(int64_t rows, const double2* 
 // them out together).  A block of 8 waves owns chunks of N consecutive tiles: wave w multiplies tiles w, w + 8, ... of the
 // chunk (the next one's loads in flight), leaves each result in LDS in the field's own layout (rows padded by one element
 // against bank conflicts), and after a barrier the block writes the chunk -- N x 4 KB (m = 16), contiguous, 1 KB per wave
-// instruction.  In place is safe: a block has read its whole chunk of P before it writes it.  Same products on the same
-// values: bit-identical to k_phaseC_p0.  rows must be a multiple of 16 N.
+// instruction.  In place (Pout == P): see the constants of the form above.  Same products on the same values:
+// bit-identical to k_phaseC_p0.  rows must be a multiple of 16 N.
 template <int M, int N>
-__global__ void __launch_bounds__(512) k_phaseC_p0_batched(int64_t rows, const double2* __restrict__ Q, const double2* P, double2* Pout,
+__global__ void __launch_bounds__(kChunkWaves * 64) k_phaseC_p0_batched(int64_t rows, const double2* __restrict__ Q, const double2* P, double2* Pout,
                                                            const double2* __restrict__ mats) {
-  constexpr int NW = 8;
+  constexpr int NW = kChunkWaves;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   constexpr int MD = (MatLds<M>::DOUBLES + 1) & ~1;
-  constexpr int RS = M + 1;                       // row stride of the staged tiles, in double2
+  constexpr int RS = chunk_row_stride(M);         // row stride of the staged tiles, in double2
   double2* const stage = reinterpret_cast<double2*>(smem + 2 * MD);  // N tiles of 16 rows x RS
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   stage_matrix<M>(smem, mats, tid, NW * 64);
@@ -575,14 +588,14 @@ __global__ void __launch_bounds__(256) k_rmul_mfma(int64_t rows, double2* __rest
 }
 
 // ... with the stores batched per chunk of N tiles through LDS (m = 16; the form of k_phaseC_p0_batched: 8 waves, the next
-// tile's loads in flight, the first tiles of the block's next chunk in flight during the stores).  y is updated in place: a
-// block has read its whole chunk before it writes it.  Same products: bit-identical to k_rmul_mfma.  rows % (16 N) == 0.
+// tile's loads in flight, the first tiles of the block's next chunk in flight during the stores).  y is updated in place (see
+// the constants of the form).  Same products: bit-identical to k_rmul_mfma.  rows % (16 N) == 0.
 template <int M, int MODE, int N>
-__global__ void __launch_bounds__(512) k_rmul_mfma_batched(int64_t rows, double2* y, const double2* __restrict__ x,
+__global__ void __launch_bounds__(kChunkWaves * 64) k_rmul_mfma_batched(int64_t rows, double2* y, const double2* __restrict__ x,
                                                            const double2* __restrict__ Cg, double b) {
-  constexpr int NW = 8;
+  constexpr int NW = kChunkWaves;
   constexpr int MD = (MatLds<M>::DOUBLES + 1) & ~1;
-  constexpr int RS = M + 1;
+  constexpr int RS = chunk_row_stride(M);
   extern __shared__ __attribute__((aligned(16))) double smem[];
   double2* const stage = reinterpret_cast<double2*>(smem + MD);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -743,11 +756,20 @@ __global__ void __launch_bounds__(256) k_phaseB8(GramFold gf, int64_t rows, cons
 
 }  // namespace
 
-// The streaming row kernels at m = 16 (phase B, k_phaseC_p0) batch their stores per chunk of tiles through LDS (k_phaseB_batched).
-// BCG_ROW_BATCHED=0 keeps the plain kernels: the A/B of record.
-static bool row_batched() {  // (read per launch, not cached: the tests switch it inside one process)
-  const char* e = std::getenv("BCG_ROW_BATCHED");
-  return e ? std::atoi(e) != 0 : true;
+static size_t mat_lds_bytes(int m) {
+  return sizeof(double) * (m == 8 ? ((MatLds<8>::DOUBLES + 1) & ~1) : m == 16 ? ((MatLds<16>::DOUBLES + 1) & ~1) : ((MatLds<32>::DOUBLES + 1) & ~1));
+}
+
+// The streaming row kernels at m = 16 (phase B, k_phaseC_p0, K5 / K6) batch their stores per chunk of tiles through LDS
+// (k_phaseB_batched): the grid of that form -- one block of kChunkWaves waves per CU -- or 0 where the plain kernel runs.
+// batched: the context's switch, read once when the context is created (BCG_ROW_BATCHED=0 keeps the plain kernels: the
+// A/B of record).
+// (m = 8 at 32^4, config 1: the batched form is slower, 0.179 against 0.169 ms -- profiles/r05_batched_stores.txt)
+// A grid capped below 8 blocks (BCG_ROW_BLOCKS_B / _C: tuning, and the odd-grid tests, which walk the plain kernels and the
+// Gram fold with fewer blocks than its 8 groups) keeps the plain kernel, as does a row count that is no whole number of chunks.
+static int row_chunk_grid(int m, int64_t rows, int max_blocks, bool batched) {
+  if (m != 16 || !batched || rows % (16 * kChunkTiles) != 0 || max_blocks < 8) return 0;
+  return static_cast<int>(std::min<int64_t>(rows / (16 * kChunkTiles), std::min(256, max_blocks)));
 }
 
 bool mfma_width(int m) { return m == 8 || m == 16 || m == 32; }  // declared in kernels.hpp
@@ -758,7 +780,7 @@ int phaseC_max_shifts(int m, bool applies_rinv) {
 }
 
 int launch_phaseB(hipStream_t s, int m, int64_t rows, double2* Q, const double2* T, const double2* negalpha,
-                  double2* partials, int max_blocks, GramFold gf, const double2* rinv, double2* Qout) {
+                  double2* partials, int max_blocks, bool batched, GramFold gf, const double2* rinv, double2* Qout) {
   if (!Qout) Qout = Q;
   const int grid = grid_tiles((rows + 15) / 16, 4, max_blocks);
   if (m == 8) {
@@ -766,13 +788,12 @@ int launch_phaseB(hipStream_t s, int m, int64_t rows, double2* Q, const double2*
     hipLaunchKernelGGL(k_phaseB8, dim3(grid), dim3(256), lds, s, gf, rows, Q, T, negalpha, partials, rinv, Qout);
   } else if (m == 16) {
     constexpr int M = 16;
-    // stores batched per chunk of 32 tiles: 6.68 against 7.42 ms at 64^4 (profiles/r05_batched_stores.txt); BCG_ROW_BATCHED=0: the plain kernel
-    if (row_batched() && rows % (16 * 32) == 0 && max_blocks >= 8) {
-      constexpr int N = 32;
-      const size_t ldsb = sizeof(double) * ((MatLds<M>::DOUBLES + 1) & ~1) * 2 + sizeof(double2) * N * 16 * (M + 1);
-      const int grid8 = static_cast<int>(std::min<int64_t>(rows / (16 * N), std::min(256, max_blocks)));
+    // stores batched per chunk of 32 tiles: 6.68 against 7.42 ms at 64^4 (profiles/r05_batched_stores.txt)
+    if (const int grid8 = row_chunk_grid(m, rows, max_blocks, batched)) {
+      constexpr int N = kChunkTiles;
+      const size_t ldsb = mat_lds_bytes(M) * 2 + chunk_stage_bytes(M, N);
       allow_lds(k_phaseB_batched<M, N>, ldsb);
-      hipLaunchKernelGGL((k_phaseB_batched<M, N>), dim3(grid8), dim3(512), ldsb, s, rows, Q, T, negalpha, partials, gf, rinv, Qout);
+      hipLaunchKernelGGL((k_phaseB_batched<M, N>), dim3(grid8), dim3(kChunkWaves * 64), ldsb, s, rows, Q, T, negalpha, partials, gf, rinv, Qout);
       return grid8;
     }
     const size_t lds = sizeof(double) * (((MatLds<M>::DOUBLES + 1) & ~1) * (rinv ? 2 : 1) + 4 * 16 * (2 * M + 2));  // TRN 2176 >= RED 2048
@@ -835,18 +856,16 @@ void launch_phaseC(hipStream_t s, int m, int64_t rows, double2* Q, double2* cons
 }
 
 void launch_phaseC_p0(hipStream_t s, int m, int64_t rows, const double2* Q, const double2* P, double2* Pout, const double2* mats,
-                      int max_blocks) {
+                      int max_blocks, bool batched) {
   // profiles/r05_phaseC_p0.txt (64^4, m = 16): the next tile's loads in flight during the products and two blocks per CU,
   // 7.26 ms per launch; without the prefetch 7.56-7.63 ms at 1024, 1536 or 2048 blocks, with it at 1024 blocks 7.84
   // stores batched per chunk of 32 tiles, one 8-wave block per CU: 6.73 against 7.25 ms at 64^4 (chunks of 16, two blocks
-  // per CU: no gain; profiles/r05_batched_stores.txt); BCG_ROW_BATCHED=0: the plain kernel
-  // (m = 8 at 32^4, config 1: the batched form is slower, 0.179 against 0.169 ms -- profiles/r05_batched_stores.txt)
-  if (m == 16 && row_batched() && rows % (16 * 32) == 0 && max_blocks >= 8) {
-    constexpr int M = 16, N = 32;
-    const size_t lds = sizeof(double) * ((MatLds<M>::DOUBLES + 1) & ~1) * 2 + sizeof(double2) * N * 16 * (M + 1);
-    const int grid8 = static_cast<int>(std::min<int64_t>(rows / (16 * N), std::min(256, max_blocks)));
+  // per CU: no gain; profiles/r05_batched_stores.txt)
+  if (const int grid8 = row_chunk_grid(m, rows, max_blocks, batched)) {
+    constexpr int M = 16, N = kChunkTiles;
+    const size_t lds = mat_lds_bytes(M) * 2 + chunk_stage_bytes(M, N);
     allow_lds(k_phaseC_p0_batched<M, N>, lds);
-    hipLaunchKernelGGL((k_phaseC_p0_batched<M, N>), dim3(grid8), dim3(512), lds, s, rows, Q, P, Pout, mats);
+    hipLaunchKernelGGL((k_phaseC_p0_batched<M, N>), dim3(grid8), dim3(kChunkWaves * 64), lds, s, rows, Q, P, Pout, mats);
     return;
   }
   const int grid = grid_tiles((rows + 15) / 16, 4, max_blocks < 512 ? max_blocks : 512);
@@ -863,9 +882,6 @@ int phaseC_multi_matrices(int nsteps, int nent, const int* first, const int* las
   int n = normalise ? nsteps : 0;
   for (int e = 0; e < nent; ++e) n += 2 * (last[e] - first[e]);
   return n;
-}
-static size_t mat_lds_bytes(int m) {
-  return sizeof(double) * (m == 8 ? ((MatLds<8>::DOUBLES + 1) & ~1) : m == 16 ? ((MatLds<16>::DOUBLES + 1) & ~1) : ((MatLds<32>::DOUBLES + 1) & ~1));
 }
 bool phaseC_multi_fits(int m, int nsteps, int n_shifts) {
   if (nsteps < 2 || nsteps > 4 || n_shifts < 1 || n_shifts > 8) return false;
@@ -915,7 +931,7 @@ void launch_phaseC_multi(hipStream_t s, int m, int64_t rows, int nsteps, const d
 }
 
 void launch_rmul_mfma(hipStream_t s, int m, int64_t rows, double2* y, const double2* x, const double2* Cd, double b,
-                      RmulMode mode, int max_blocks) {
+                      RmulMode mode, int max_blocks, bool batched) {
   const int grid = grid_tiles((rows + 15) / 16, 4, max_blocks);
 #define BCG_RMUL(MM)                                                                                             \
   {                                                                                                              \
@@ -925,20 +941,19 @@ void launch_rmul_mfma(hipStream_t s, int m, int64_t rows, double2* y, const doub
     else if (mode == RMUL_XPAY) hipLaunchKernelGGL((k_rmul_mfma<M, RMUL_XPAY>), dim3(grid), dim3(256), lds, s, rows, y, x, Cd, b); \
     else hipLaunchKernelGGL((k_rmul_mfma<M, RMUL_MUL>), dim3(grid), dim3(256), lds, s, rows, y, x, Cd, b);       \
   }
-  // m = 16: stores batched per chunk of 32 tiles (k_phaseC_p0_batched's form; BCG_ROW_BATCHED=0: the plain kernel)
-  if (m == 16 && row_batched() && rows % (16 * 32) == 0 && max_blocks >= 8) {
-    constexpr int M = 16, N = 32;
-    const size_t ldsb = sizeof(double) * ((MatLds<M>::DOUBLES + 1) & ~1) + sizeof(double2) * N * 16 * (M + 1);
-    const int grid8 = static_cast<int>(std::min<int64_t>(rows / (16 * N), std::min(256, max_blocks)));
+  // m = 16: stores batched per chunk of 32 tiles
+  if (const int grid8 = row_chunk_grid(m, rows, max_blocks, batched)) {
+    constexpr int M = 16, N = kChunkTiles;
+    const size_t ldsb = mat_lds_bytes(M) + chunk_stage_bytes(M, N);
     if (mode == RMUL_ADD) {
       allow_lds(k_rmul_mfma_batched<M, RMUL_ADD, N>, ldsb);
-      hipLaunchKernelGGL((k_rmul_mfma_batched<M, RMUL_ADD, N>), dim3(grid8), dim3(512), ldsb, s, rows, y, x, Cd, b);
+      hipLaunchKernelGGL((k_rmul_mfma_batched<M, RMUL_ADD, N>), dim3(grid8), dim3(kChunkWaves * 64), ldsb, s, rows, y, x, Cd, b);
     } else if (mode == RMUL_XPAY) {
       allow_lds(k_rmul_mfma_batched<M, RMUL_XPAY, N>, ldsb);
-      hipLaunchKernelGGL((k_rmul_mfma_batched<M, RMUL_XPAY, N>), dim3(grid8), dim3(512), ldsb, s, rows, y, x, Cd, b);
+      hipLaunchKernelGGL((k_rmul_mfma_batched<M, RMUL_XPAY, N>), dim3(grid8), dim3(kChunkWaves * 64), ldsb, s, rows, y, x, Cd, b);
     } else {
       allow_lds(k_rmul_mfma_batched<M, RMUL_MUL, N>, ldsb);
-      hipLaunchKernelGGL((k_rmul_mfma_batched<M, RMUL_MUL, N>), dim3(grid8), dim3(512), ldsb, s, rows, y, x, Cd, b);
+      hipLaunchKernelGGL((k_rmul_mfma_batched<M, RMUL_MUL, N>), dim3(grid8), dim3(kChunkWaves * 64), ldsb, s, rows, y, x, Cd, b);
     }
     return;
   }

@@ -21,8 +21,10 @@ struct GramFold {
 };
 
 // Phase B: [Q <- Q * rinv if rinv] ; Q += T * negalpha ; partials of (new Q)^dagger (new Q).  Returns blocks used.
+// batched (here, launch_phaseC_p0, launch_rmul_mfma): the context's row_batched -- at m = 16 the form that stages chunks
+// of tiles in LDS and writes them out together, where the row count allows it
 int launch_phaseB(hipStream_t s, int m, int64_t rows, double2* Q, const double2* T, const double2* negalpha,
-                  double2* partials, int max_blocks, GramFold fold = GramFold(), const double2* rinv = nullptr,
+                  double2* partials, int max_blocks, bool batched, GramFold fold = GramFold(), const double2* rinv = nullptr,
                   double2* Qout = nullptr);  // Qout: the new Q goes there and Q is left as it was (nullptr: in place)
 // Phase C: q = Q*mats[0] if apply_rinv (1: stored back to Q; 2: used, not stored); for k < nshift:
 // X[k] += P[k]*mats[1+2k]; P[k] <- P[k]*mats[2+2k] + q.
@@ -44,9 +46,9 @@ void launch_phaseC_multi(hipStream_t s, int m, int64_t rows, int nsteps, const d
                          bool normalise = true, int xacc = 0, const double2* p1 = nullptr, double2* Y = nullptr);
 // Shift 0's phase C with the update of X_0 deferred (m = 8, 16): Pout = P mats[1] + Q mats[0]; mats = [rinv, B]
 void launch_phaseC_p0(hipStream_t s, int m, int64_t rows, const double2* Q, const double2* P, double2* Pout, const double2* mats,
-                      int max_blocks);
+                      int max_blocks, bool batched);
 void launch_rmul_mfma(hipStream_t s, int m, int64_t rows, double2* y, const double2* x, const double2* Cd, double b,
-                      RmulMode mode, int max_blocks);
+                      RmulMode mode, int max_blocks, bool batched);
 int launch_gram_mfma(hipStream_t s, int m, int64_t rows, const double2* a, const double2* b, double2* partials,
                      int max_blocks);
 // Pacing counters of the specialised stencil (kernels_stencil.hip, HopWalk::sync); owned by the context.

@@ -4,8 +4,6 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include "kernels.hpp"
 #include "kernels_mfma.hpp"
 

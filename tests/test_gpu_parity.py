@@ -953,6 +953,50 @@ def test_batched_row_kernels_against_the_plain_ones(bc, orc, monkeypatch):
         assert rel_err(out["1"][2][s], o["X"][s]) < 1e-10
 
 
+def test_batched_row_kernels_on_a_grid_smaller_than_a_block_of_waves(bc, orc, monkeypatch):
+    """m = 16 on [8, 4, 4, 4]: 1536 rows are three chunks of 32 tiles, so the batched kernels run on three blocks -- fewer
+    than the eight waves of one -- every block has a single chunk, and none prefetches a next one.  The switch is read when
+    the context is created: one context per setting.  K5 / K6 do the same products on the same values as the plain kernels
+    (BCG_ROW_BATCHED=0): bit-identical.  (The library has no caller of the third form, y = y C: no field method reaches it.)
+    A short grouped solve runs phase B and k_phaseC_p0 on the same grid.  Phase B's Gram partial sums take another order in
+    the batched form, so the two solves agree to rounding (the bound of the sibling test above, for fewer iterations) and
+    NOT bit for bit: that they differ at all is what shows that the context's switch reaches the launchers."""
+    m, dims, mass, shifts = 16, [8, 4, 4, 4], 0.2, [0.0, 0.1]
+    assert int(np.prod(dims)) * 3 == 3 * 512
+    U = orc.fill_gauge(dims, 98)
+    Bh = orc.fill_field(m, int(np.prod(dims)), 95)
+    Xh = orc.fill_field(m, int(np.prod(dims)), 96)
+    rng = np.random.default_rng(97)
+    C = (rng.standard_normal((m, m)) + 1j * rng.standard_normal((m, m))) * 0.2
+    out = {}
+    for batched in ("1", "0"):
+        monkeypatch.setenv("BCG_ROW_BATCHED", batched)
+        ctx = bc.Context(dims)
+        x = bc.block_fermion_field(ctx, m, Xh)
+        y = bc.block_fermion_field(ctx, m, Bh)
+        y.add(x, C)                # K5, inc/fields.hpp:70-77
+        k5 = y.download()
+        y.rescale_add(C, x, 0.5)   # K6, inc/fields.hpp:79-90
+        k6 = y.download()
+        D = bc.dirac_op(ctx, mass, U=U)
+        B = bc.block_fermion_field(ctx, m, Bh)
+        X = [bc.block_fermion_field(ctx, m) for _ in shifts]
+        st = bc.SBCGrQState(X, B, D, shifts, 0.0, 0.0)
+        st.iterate(6)
+        res = st.residual
+        st.end()
+        out[batched] = (k5, k6, [f.download() for f in X], res)
+        ctx.close()
+    assert np.isfinite(out["1"][1]).all()
+    assert np.array_equal(out["1"][0], out["0"][0])
+    assert np.array_equal(out["1"][1], out["0"][1])
+    for s in range(len(shifts)):
+        print("shift", s, "rel_err batched vs plain", rel_err(out["1"][2][s], out["0"][2][s]))
+        assert rel_err(out["1"][2][s], out["0"][2][s]) < 1e-12, s
+    assert abs(out["1"][3] - out["0"][3]) <= 1e-12 * out["0"][3]
+    assert any(not np.array_equal(out["1"][2][s], out["0"][2][s]) for s in range(len(shifts)))
+
+
 def test_grouping_randomised_schedules(bc, orc, monkeypatch):
     """Seeded random schedules through the solver's state machine: width 8 / 16, 1 ... 8 shifts of random size (so that some
     retire early, some never), group depth 2 ... 4, X_0 deferred or not, the iterations asked for in random pieces (a piece
