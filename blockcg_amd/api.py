@@ -264,6 +264,29 @@ class block_fermion_field:
         self.ctx.check(self.ctx.lib.bcg_field_slice_dot(self.h, rhs.h, int(dir), _dp(out)))
         return out
 
+    def slice_gram(self, rhs, dir, momenta=None):
+        """Per-slice Gram matrices: [L_dir global, N_rhs, N_rhs] with entry (t, i, j) = sum over the sites of slice x_dir = t
+        and the colours of conj(this[.., i]) * rhs[.., j]; its sum over t is hermitian_dot(rhs), its diagonal slice_dot.
+        momenta: a list of integer momenta (ndim or 4 entries each, the entry along dir 0) gives [P, L_dir, N_rhs, N_rhs]
+        with the summand weighted by exp(-2 pi i sum_mu n_mu x_mu / L_mu) of the GLOBAL coordinates.  Summed over ranks."""
+        if not 0 <= int(dir) < self.ctx.ndim:
+            raise BlockCGError(1, "slice_gram: direction outside the lattice")
+        m, L = self.N_rhs, self.ctx.dims[int(dir)]
+        if momenta is None:
+            out = np.empty((L, m, m), dtype=np.complex128)
+            self.ctx.check(self.ctx.lib.bcg_field_slice_gram(self.h, rhs.h, int(dir), 0, None, _dp(out)))
+            return np.ascontiguousarray(out.transpose(0, 2, 1))
+        mom = [list(p) for p in momenta]
+        if not mom or any(len(p) > 4 for p in mom):
+            raise BlockCGError(1, "slice_gram: momenta is a non-empty list of up to 4 integers each")
+        ns = np.zeros((len(mom), 4), dtype=np.intc)
+        for k, p in enumerate(mom):
+            ns[k, :len(p)] = p
+        out = np.empty((len(mom), L, m, m), dtype=np.complex128)
+        self.ctx.check(self.ctx.lib.bcg_field_slice_gram(self.h, rhs.h, int(dir), len(mom), ns.ctypes.data_as(_lib.c_int_p),
+                                                         _dp(out)))
+        return np.ascontiguousarray(out.transpose(0, 1, 3, 2))
+
     def __iadd__(self, rhs):
         self.ctx.check(self.ctx.lib.bcg_field_add_assign(self.h, rhs.h))
         return self

@@ -1,7 +1,9 @@
 // include/blockcg_hip.h: what goes into a solve and what comes out of it without passing through host memory -- noise fields
 // (bcg_field_fill_noise), point and wall sources (bcg_field_set_point_sources, bcg_field_set_wall_sources) and the inner
-// product per slice and column (bcg_field_slice_dot).  Kernels: kernels_sources.hip.
+// product per slice and column (bcg_field_slice_dot); and the per-slice Gram matrices with momentum projection
+// (bcg_field_slice_gram).  Kernels: kernels_sources.hip, kernels_slice_gram.hip.
 #include "capi_internal.hpp"
+#include "kernels_slice_gram.hpp"
 #include "kernels_sources.hpp"
 
 namespace bcg_impl {
@@ -15,6 +17,15 @@ bool colours_ok(const int* colour, int m) {
   for (int j = 0; j < m; ++j)
     if (colour[j] < 0 || colour[j] > 2) return false;
   return true;
+}
+
+// exp(-2 pi i k / L) for k = (n x) mod L, reduced exactly in integers; n any integer, x a global coordinate
+double2 momentum_phase(int n, int x, int L) {
+  const int64_t nn = ((static_cast<int64_t>(n) % L) + L) % L;
+  const int64_t k = (nn * x) % L;
+  if (k == 0) return make_double2(1.0, 0.0);
+  const double th = 2.0 * M_PI * static_cast<double>(k) / static_cast<double>(L);
+  return make_double2(std::cos(th), -std::sin(th));
 }
 
 }  // namespace
@@ -127,6 +138,73 @@ int bcg_field_slice_dot(const bcg_field* a, const bcg_field* b, int dir, double*
       BCG_FAIL(c, BCG_ERR_COMM, "allreduce_sum callback failed");
   }
   HIP_TRY(c, hipMemcpyAsync(out, reduced, static_cast<size_t>(n_out) * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
+  return stream_sync(c);
+}
+
+int bcg_field_slice_gram(const bcg_field* a, const bcg_field* b, int dir, int n_mom, const int* momenta, double* out) {
+  DeviceScope on_device(a ? a->ctx : nullptr);
+  if (!same_shape(a, b) || !out) return BCG_ERR_INVALID;
+  bcg_context* c = a->ctx;
+  if (dir < 0 || dir >= c->ndim) BCG_FAIL(c, BCG_ERR_INVALID, "bcg_field_slice_gram: direction outside the lattice");
+  if (n_mom < 0 || (n_mom > 0 && !momenta)) BCG_FAIL(c, BCG_ERR_INVALID, "bcg_field_slice_gram: n_mom momenta are needed");
+  for (int p = 0; p < n_mom; ++p)
+    for (int mu = 0; mu < 4; ++mu)
+      if ((mu == dir || mu >= c->ndim) && momenta[4 * p + mu] != 0)
+        BCG_FAIL(c, BCG_ERR_INVALID, "bcg_field_slice_gram: momentum component along dir or beyond the lattice's dimensions");
+  if (c->distributed && (!c->have_comm || !c->comm.allreduce_sum))
+    BCG_FAIL(c, BCG_ERR_COMM, "lattice is split over ranks but no bcg_comm was set");
+  const int m = a->m;
+  const int Lg = c->gdims[dir];
+  const int64_t per = static_cast<int64_t>(Lg) * m * m;  // entries of one momentum
+  const bool mfma = fast_rows(c, m);
+  bcg::SliceGramPlan plan;
+  if (per > kSliceHalf || !bcg::slice_gram_plan(m, mfma, c->lat, a->parity, dir, Lg, n_mom, kSliceHalf, &plan))
+    BCG_FAIL(c, BCG_ERR_UNSUPPORTED, "bcg_field_slice_gram: one momentum's slices do not fit the context's scratch");
+  BCG_TRY(ensure_scratch(c));
+  // c->partials: [phase tables][block partials] in the first half, the reduced [pc][L_dir global][m^2] in the second
+  const int64_t tab_entries = bcg::slice_gram_table_entries(plan);
+  double2* const tab_dev = c->partials;
+  double2* const partials = c->partials + tab_entries;
+  double2* const reduced = c->partials + kSliceHalf;
+  const int P = n_mom > 0 ? n_mom : 1;
+  // the tables of every momentum (a launch's unused momenta: ones), from global coordinates: nothing depends on the grid
+  std::vector<double2> tabs;
+  const int64_t per_tab = static_cast<int64_t>(3) * plan.ltab;
+  if (n_mom > 0) {
+    tabs.assign(static_cast<size_t>(per_tab) * (P + plan.pc), make_double2(1.0, 0.0));
+    for (int p = 0; p < P; ++p)
+      for (int s = 0; s < 3; ++s) {
+        const int mu = plan.mu[s];
+        for (int x = 0; x < c->lat.L[mu]; ++x)
+          tabs[p * per_tab + static_cast<int64_t>(s) * plan.ltab + x] = momentum_phase(momenta[4 * p + mu], c->lat.origin[mu] + x, c->gdims[mu]);
+      }
+  }
+  for (int p0 = 0; p0 < P; p0 += plan.pc) {
+    const int n = std::min(plan.pc, P - p0);
+    const int pc = bcg::slice_gram_launch_pc(n);
+    if (n_mom > 0)
+      HIP_TRY(c, hipMemcpyAsync(tab_dev, tabs.data() + p0 * per_tab, static_cast<size_t>(pc * per_tab) * sizeof(double2),
+                                hipMemcpyHostToDevice, c->stream));
+    {
+      ProfScope ps(c, "slice_gram", row_bytes(a, a == b ? 1 : 2), product_flops(a, pc));
+      bcg::launch_slice_gram(c->stream, m, mfma, c->lat, a->parity, dir, plan, pc, a->d, b->d, n_mom > 0 ? tab_dev : nullptr, partials);
+    }
+    BCG_TRY(check_launch(c, "slice_gram"));
+    const size_t n_red = static_cast<size_t>(n) * per;
+    if (c->lat.split[dir])  // the slices of the other ranks: zeros from this one
+      HIP_TRY(c, hipMemsetAsync(reduced, 0, n_red * sizeof(double2), c->stream));
+    {
+      ProfScope ps(c, "slice_gram_fold");
+      bcg::launch_slice_gram_fold(c->stream, m, pc, n, c->lat.L[dir], Lg, plan.nbps, c->lat.origin[dir], partials, reduced);
+    }
+    BCG_TRY(check_launch(c, "slice_gram_fold"));
+    if (c->distributed) {
+      ProfScope ps(c, "allreduce");
+      if (c->comm.allreduce_sum(c->comm.user, reduced, 2 * n_red) != 0) BCG_FAIL(c, BCG_ERR_COMM, "allreduce_sum callback failed");
+    }
+    HIP_TRY(c, hipMemcpyAsync(out + 2 * static_cast<size_t>(p0) * per, reduced, n_red * sizeof(double2), hipMemcpyDeviceToHost,
+                              c->stream));
+  }
   return stream_sync(c);
 }
 

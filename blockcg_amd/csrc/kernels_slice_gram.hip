@@ -1,0 +1,360 @@
+// Per-slice Gram matrices with momentum projection (gfx950): C_p(t) = sum_{x_dir = t} w_p(x) a(x)^dagger b(x), all column
+// pairs, PC momenta per pass over the operands.  The walk, the launch plan and the layouts: kernels_slice_gram.hpp.
+// m = 16 and 32: v_mfma_f64_16x16x4_f64 through gram_step / GramAcc of mfma_common.hpp; every other width: one VALU
+// kernel with the rows of a chunk staged in LDS.  Plain stores, no atomics; 64-bit wherever an element offset is formed.
+#include "kernels_slice_gram.hpp"
+#include "mfma_common.hpp"
+
+namespace bcg {
+
+namespace {
+
+struct SGGeom {
+  int n_virtual;  // rows of one slice (half0: counting the skipped sites)
+  int run;        // rows per run
+  int inner;      // sites per run
+  int chunk;      // rows per block
+  int Leff;       // runs between those of consecutive o: L (half0: L0 / 2)
+  int nbps;       // blocks per slice
+  int half0;      // half field, dir = 0
+  int half;       // half field, dir > 0: slot 0 is the compact x0
+  int e0, e1;     // extents of slots 0 and 1 in the slice's site index c0 + e0 (c1 + e1 c2)
+  int par_off;    // half fields: field parity + parity of the local origin
+  int ltab;       // entries per phase table
+};
+
+struct SGRow {
+  int64_t row;  // row of the field
+  bool ok;      // it exists and the field holds it
+  int x[3];     // local coordinates of its site along the three slots (0 where !ok)
+};
+
+// virtual row v = o * run + e of slice t; live: v is inside the block's chunk
+template <bool COORDS>
+__device__ __forceinline__ SGRow sg_row(const SGGeom& g, int t, int teff, int o, int e, bool live) {
+  SGRow r;
+  r.ok = live;
+  r.row = (static_cast<int64_t>(o) * g.Leff + teff) * g.run + e;
+  r.x[0] = r.x[1] = r.x[2] = 0;
+  if (COORDS || g.half0) {
+    const int idx = live ? o * g.inner + e / 3 : 0;
+    const int q = idx / g.e0;
+    const int c0 = idx - q * g.e0;
+    const int c2 = q / g.e1;
+    const int c1 = q - c2 * g.e1;
+    if (g.half0) r.ok = live && ((c0 + c1 + c2 + g.par_off + t) & 1) == 0;
+    r.x[0] = g.half ? 2 * c0 + ((c1 + c2 + t + g.par_off) & 1) : c0;
+    r.x[1] = c1;
+    r.x[2] = c2;
+  }
+  return r;
+}
+
+__device__ __forceinline__ double2 cmul(double2 a, double2 b) {
+  return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
+}
+// w_p of a site: the three table entries multiplied in ascending direction
+__device__ __forceinline__ double2 sg_phase(const double2* __restrict__ tab, int ltab, int p, const int x[3]) {
+  const double2* tp = tab + static_cast<int64_t>(p) * 3 * ltab;
+  return cmul(cmul(tp[x[0]], tp[ltab + x[1]]), tp[2 * ltab + x[2]]);
+}
+
+__device__ __forceinline__ void cfma_conj(double2& acc, double2 a, double2 b) {
+  acc.x = fma(a.x, b.x, acc.x);
+  acc.x = fma(a.y, b.y, acc.x);
+  acc.y = fma(a.x, b.y, acc.y);
+  acc.y = fma(-a.y, b.x, acc.y);
+}
+
+// gram_block_store of mfma_common.hpp with the destination given: the per-wave fragments summed in wave order, one 16 x 16
+// block at a time through red (NW * 8 * 64 doubles), dst[j * M + i]
+template <int M, int NW>
+__device__ __forceinline__ void sg_block_store(const GramAcc<M>& G, double* red, double2* __restrict__ dst, int tid) {
+  constexpr int JB = M / 16;
+  const int wave = tid >> 6, lane = tid & 63;
+#pragma unroll
+  for (int q = 0; q < JB * JB; ++q) {
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      red[(wave * 8 + r) * 64 + lane] = G.re[q][r];
+      red[(wave * 8 + 4 + r) * 64 + lane] = G.im[q][r];
+    }
+    __syncthreads();
+    for (int e = tid; e < 4 * 64; e += NW * 64) {
+      const int l = e & 63, r = (e >> 6) & 3;
+      double sr = 0.0, si = 0.0;
+#pragma unroll
+      for (int w = 0; w < NW; ++w) {
+        sr += red[(w * 8 + r) * 64 + l];
+        si += red[(w * 8 + 4 + r) * 64 + l];
+      }
+      const int i = 16 * (q / JB) + (l >> 4) + 4 * r, j = 16 * (q % JB) + (l & 15);
+      dst[j * M + i] = make_double2(sr, si);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// m = 16, 32.  Wave w of block (t, k) takes the quads w, w + 4, ... of the chunk; lane l owns row 4 q + (l >> 4) of a quad
+// and column (l & 15) + 16 jb.  A quad may straddle sites and runs, so every lane derives its own row's address, validity
+// and phase; the loop bound is the chunk's quad count, the same for all lanes of a wave.
+// ---------------------------------------------------------------------------------------------
+template <int M, int PC, bool PHASE, bool SELF>
+__global__ void __launch_bounds__(256) k_slice_gram_mfma(SGGeom g, const double2* __restrict__ a, const double2* __restrict__ b,
+                                                         const double2* __restrict__ tab, double2* __restrict__ partials) {
+  constexpr int NW = 4, JB = M / 16, U = M == 16 ? 4 : 2;
+  __shared__ __attribute__((aligned(16))) double red[NW * 8 * 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int t = blockIdx.x / g.nbps, k = blockIdx.x - t * g.nbps;
+  const int teff = g.half0 ? t >> 1 : t;
+  const int r0 = k * g.chunk;
+  const int r1 = r0 + g.chunk < g.n_virtual ? r0 + g.chunk : g.n_virtual;
+  const int nq = (r1 - r0 + 3) >> 2;
+  const int col = lane & 15;
+  GramAcc<M> G[PC];
+#pragma unroll
+  for (int p = 0; p < PC; ++p) gram_zero(G[p]);
+  int v = r0 + 4 * wave + (lane >> 4);
+  int o = v / g.run, e = v - o * g.run;
+  const int step_o = (4 * NW) / g.run, step_e = (4 * NW) % g.run;
+  for (int q = wave; q < nq; q += NW * U) {
+    SGRow rw[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      rw[u] = sg_row<PHASE>(g, t, teff, o, e, v < r1);
+      v += 4 * NW;
+      o += step_o;
+      e += step_e;
+      if (e >= g.run) {
+        e -= g.run;
+        o += 1;
+      }
+    }
+    double2 av[U][JB], bv[U][JB];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int jb = 0; jb < JB; ++jb) {
+        const int64_t ad = rw[u].row * M + 16 * jb + col;
+        av[u][jb] = rw[u].ok ? a[ad] : make_double2(0.0, 0.0);
+        bv[u][jb] = SELF ? av[u][jb] : (rw[u].ok ? b[ad] : make_double2(0.0, 0.0));
+      }
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int p = 0; p < PC; ++p) {
+        if (PHASE) {
+          const double2 w = sg_phase(tab, g.ltab, p, rw[u].x);
+          double2 bw[JB];
+#pragma unroll
+          for (int jb = 0; jb < JB; ++jb) bw[jb] = cmul(bv[u][jb], w);
+          gram_step<M>(G[p], av[u], bw);
+        } else {
+          gram_step<M>(G[p], av[u], bv[u]);
+        }
+      }
+  }
+#pragma unroll
+  for (int p = 0; p < PC; ++p)
+    sg_block_store<M, NW>(G[p], red, partials + (static_cast<int64_t>(blockIdx.x) * PC + p) * (M * M), tid);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Every other width.  R rows of the chunk at a time are staged in LDS (b already multiplied by the PC phases of its site),
+// lane `tid` owns a 2 x 2 tile of (i, j) pairs (four operand reads per staged row for its four products) and walks the
+// staged rows.
+// ---------------------------------------------------------------------------------------------
+constexpr int kSGRows = 16;
+
+template <int PC, bool PHASE, bool SELF>
+__global__ void __launch_bounds__(256) k_slice_gram_generic(int m, SGGeom g, const double2* __restrict__ a,
+                                                            const double2* __restrict__ b, const double2* __restrict__ tab,
+                                                            double2* __restrict__ partials) {
+  constexpr int R = kSGRows;
+  __shared__ double2 As[R * 32];
+  __shared__ double2 Bs[PC][R * 32];
+  const int tid = threadIdx.x;
+  const int t = blockIdx.x / g.nbps, k = blockIdx.x - t * g.nbps;
+  const int teff = g.half0 ? t >> 1 : t;
+  const int r0 = k * g.chunk;
+  const int r1 = r0 + g.chunk < g.n_virtual ? r0 + g.chunk : g.n_virtual;
+  const int mm = m * m;
+  // the lane's pairs: the 2 x 2 tile (i0 + di, j0 + dj), u = 2 dj + di, of the (m + 1) / 2 squared tiles (at most 256)
+  const int mt = (m + 1) >> 1;
+  const int j0 = 2 * (tid / mt), i0 = 2 * (tid - (tid / mt) * mt);
+  const bool mine = tid < mt * mt;
+  const int i1 = i0 + 1 < m ? i0 + 1 : i0, j1 = j0 + 1 < m ? j0 + 1 : j0;  // clamped: the pair is dropped at the store
+  double2 acc[PC][4];
+#pragma unroll
+  for (int p = 0; p < PC; ++p)
+#pragma unroll
+    for (int u = 0; u < 4; ++u) acc[p][u] = make_double2(0.0, 0.0);
+  for (int base = r0; base < r1; base += R) {
+    __syncthreads();
+    for (int x = tid; x < R * m; x += 256) {
+      const int r = x / m, j = x - r * m;
+      const int v = base + r;
+      const bool live = v < r1;
+      const int vv = live ? v : r0;
+      const int o = vv / g.run, e = vv - o * g.run;
+      const SGRow rw = sg_row<PHASE>(g, t, teff, o, e, live);
+      const int64_t ad = rw.row * m + j;
+      const double2 av = rw.ok ? a[ad] : make_double2(0.0, 0.0);
+      const double2 bv = SELF ? av : (rw.ok ? b[ad] : make_double2(0.0, 0.0));
+      As[x] = av;
+#pragma unroll
+      for (int p = 0; p < PC; ++p) Bs[p][x] = PHASE ? cmul(bv, sg_phase(tab, g.ltab, p, rw.x)) : bv;
+    }
+    __syncthreads();
+    if (mine) {
+      for (int r = 0; r < R; ++r) {
+        const double2 a0 = As[r * m + i0], a1 = As[r * m + i1];
+#pragma unroll
+        for (int p = 0; p < PC; ++p) {
+          const double2 b0 = Bs[p][r * m + j0], b1 = Bs[p][r * m + j1];
+          cfma_conj(acc[p][0], a0, b0);
+          cfma_conj(acc[p][1], a1, b0);
+          cfma_conj(acc[p][2], a0, b1);
+          cfma_conj(acc[p][3], a1, b1);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int p = 0; p < PC; ++p)
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int i = i0 + (u & 1), j = j0 + (u >> 1);
+      if (mine && i < m && j < m) partials[(static_cast<int64_t>(blockIdx.x) * PC + p) * mm + j * m + i] = acc[p][u];
+    }
+}
+
+__global__ void __launch_bounds__(256) k_slice_gram_fold(int mm, int pc, int np, int L_local, int L_global, int nbps, int origin,
+                                                         const double2* __restrict__ partials, double2* __restrict__ out) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= static_cast<int64_t>(np) * L_local * mm) return;
+  const int e = static_cast<int>(i % mm);
+  const int64_t r = i / mm;
+  const int t = static_cast<int>(r % L_local), p = static_cast<int>(r / L_local);
+  double2 s = make_double2(0.0, 0.0);
+  for (int k = 0; k < nbps; ++k) {
+    const double2 v = partials[((static_cast<int64_t>(t) * nbps + k) * pc + p) * mm + e];
+    s.x += v.x;
+    s.y += v.y;
+  }
+  out[(static_cast<int64_t>(p) * L_global + origin + t) * mm + e] = s;
+}
+
+template <int M, int PC, bool PHASE>
+void launch_mfma(hipStream_t s, unsigned blocks, const SGGeom& g, const double2* a, const double2* b, const double2* tab,
+                 double2* partials) {
+  if (a == b) hipLaunchKernelGGL((k_slice_gram_mfma<M, PC, PHASE, true>), dim3(blocks), dim3(256), 0, s, g, a, b, tab, partials);
+  else hipLaunchKernelGGL((k_slice_gram_mfma<M, PC, PHASE, false>), dim3(blocks), dim3(256), 0, s, g, a, b, tab, partials);
+}
+template <int PC, bool PHASE>
+void launch_generic(hipStream_t s, unsigned blocks, int m, const SGGeom& g, const double2* a, const double2* b, const double2* tab,
+                    double2* partials) {
+  if (a == b) hipLaunchKernelGGL((k_slice_gram_generic<PC, PHASE, true>), dim3(blocks), dim3(256), 0, s, m, g, a, b, tab, partials);
+  else hipLaunchKernelGGL((k_slice_gram_generic<PC, PHASE, false>), dim3(blocks), dim3(256), 0, s, m, g, a, b, tab, partials);
+}
+
+// rows of one slice, rows and sites per run
+void slice_rows(const LatticeDev& lat, int parity, int dir, int64_t* n_virtual, int64_t* run, int64_t* inner) {
+  const int L = lat.L[dir];
+  if (parity >= 0 && dir == 0) {
+    *inner = 1;
+    *run = 3;
+    *n_virtual = lat.V / L * 3;  // every (x1, x2, x3); half of them hold x0 = t
+  } else {
+    *inner = parity >= 0 ? lat.stride[dir] / 2 : lat.stride[dir];  // half: x0 is compact
+    *run = *inner * 3;
+    *n_virtual = lat.V / (lat.stride[dir] * L) * *run;
+  }
+}
+
+bool use_mfma(int m, bool mfma) { return mfma && (m == 16 || m == 32); }
+
+}  // namespace
+
+int slice_gram_launch_pc(int n) { return n <= 1 ? 1 : n <= 2 ? 2 : 4; }
+
+bool slice_gram_plan(int m, bool mfma, const LatticeDev& lat, int parity, int dir, int L_global, int n_mom, int64_t half_entries,
+                     SliceGramPlan* plan) {
+  const int64_t mm = static_cast<int64_t>(m) * m;
+  const int L = lat.L[dir];
+  int n = 0;
+  plan->ltab = 1;
+  for (int mu = 0; mu < 4; ++mu)
+    if (mu != dir) {
+      plan->mu[n++] = mu;
+      if (lat.L[mu] > plan->ltab) plan->ltab = lat.L[mu];
+    }
+  const int pc_max = use_mfma(m, mfma) && m == 16 ? 4 : 2;
+  int pc = 1;
+  while (2 * pc <= pc_max && 2 * pc <= n_mom && 2 * pc * L_global * mm <= half_entries) pc *= 2;
+  if (pc * L_global * mm > half_entries) return false;
+  plan->pc = pc;
+  int64_t n_virtual, run, inner;
+  slice_rows(lat, parity, dir, &n_virtual, &run, &inner);
+  if (n_virtual >= (int64_t(1) << 30)) return false;
+  const int64_t room = half_entries - slice_gram_table_entries(*plan);
+  if (room <= 0) return false;
+  int64_t budget = room / (pc * mm);
+  if (budget > 2048) budget = 2048;
+  int64_t nbps = budget / L;
+  const int64_t most = (n_virtual + 63) / 64;
+  if (nbps > most) nbps = most;
+  if (nbps < 1) nbps = 1;
+  const int64_t chunk = ((n_virtual + nbps - 1) / nbps + 15) / 16 * 16;
+  nbps = (n_virtual + chunk - 1) / chunk;
+  if (nbps * L > budget) return false;
+  plan->nbps = static_cast<int>(nbps);
+  plan->chunk = static_cast<int>(chunk);
+  return true;
+}
+
+void launch_slice_gram(hipStream_t s, int m, bool mfma, const LatticeDev& lat, int parity, int dir, const SliceGramPlan& plan, int pc,
+                       const double2* a, const double2* b, const double2* tab, double2* partials) {
+  int64_t n_virtual, run, inner;
+  slice_rows(lat, parity, dir, &n_virtual, &run, &inner);
+  SGGeom g{};
+  g.n_virtual = static_cast<int>(n_virtual);
+  g.run = static_cast<int>(run);
+  g.inner = static_cast<int>(inner);
+  g.chunk = plan.chunk;
+  g.nbps = plan.nbps;
+  g.half0 = parity >= 0 && dir == 0;
+  g.half = parity >= 0 && dir != 0;
+  g.Leff = g.half0 ? lat.L[0] / 2 : lat.L[dir];
+  g.e0 = g.half ? lat.L[0] / 2 : lat.L[plan.mu[0]];
+  g.e1 = lat.L[plan.mu[1]];
+  g.par_off = parity >= 0 ? parity + ((lat.origin[0] + lat.origin[1] + lat.origin[2] + lat.origin[3]) & 1) : 0;
+  g.ltab = plan.ltab;
+  const unsigned blocks = static_cast<unsigned>(plan.nbps) * static_cast<unsigned>(lat.L[dir]);
+  if (use_mfma(m, mfma)) {
+    if (m == 16) {
+      if (!tab) launch_mfma<16, 1, false>(s, blocks, g, a, b, tab, partials);
+      else if (pc == 1) launch_mfma<16, 1, true>(s, blocks, g, a, b, tab, partials);
+      else if (pc == 2) launch_mfma<16, 2, true>(s, blocks, g, a, b, tab, partials);
+      else launch_mfma<16, 4, true>(s, blocks, g, a, b, tab, partials);
+    } else {
+      if (!tab) launch_mfma<32, 1, false>(s, blocks, g, a, b, tab, partials);
+      else if (pc == 1) launch_mfma<32, 1, true>(s, blocks, g, a, b, tab, partials);
+      else launch_mfma<32, 2, true>(s, blocks, g, a, b, tab, partials);
+    }
+  } else {
+    if (!tab) launch_generic<1, false>(s, blocks, m, g, a, b, tab, partials);
+    else if (pc == 1) launch_generic<1, true>(s, blocks, m, g, a, b, tab, partials);
+    else launch_generic<2, true>(s, blocks, m, g, a, b, tab, partials);
+  }
+}
+
+void launch_slice_gram_fold(hipStream_t s, int m, int pc, int np, int L_local, int L_global, int nbps, int origin,
+                            const double2* partials, double2* out) {
+  const int64_t n = static_cast<int64_t>(np) * L_local * m * m;
+  hipLaunchKernelGGL(k_slice_gram_fold, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, s, m * m, pc, np, L_local, L_global,
+                     nbps, origin, partials, out);
+}
+
+}  // namespace bcg

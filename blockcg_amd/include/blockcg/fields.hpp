@@ -225,6 +225,23 @@ class block_fermion_field {
     blockcg::check(bcg_field_slice_dot(f_, rhs.f_, dir, reinterpret_cast<double*>(out.data())), lat_->ctx(), "slice_dot");
     return out;
   }
+  // Per-slice Gram matrices: entry t (global) is the matrix whose (i, j) is the sum over the sites of slice x_dir = t and
+  // the colours of conj(this column i) * rhs column j -- hermitian_dot resolved by slice (its diagonal: slice_dot)
+  std::vector<block_matrix<N_rhs>> slice_gram(const block_fermion_field& rhs, int dir) const {
+    return slice_gram_call(rhs, dir, 0, nullptr);
+  }
+  // ... projected on momenta: entry p * L_dir + t, the summand weighted by exp(-2 pi i sum_mu n_mu x_mu / L_mu) with
+  // n = momenta[p] (up to 4 integers, missing ones 0; the one along dir must be 0) and x the GLOBAL coordinates
+  std::vector<block_matrix<N_rhs>> slice_gram(const block_fermion_field& rhs, int dir,
+                                              const std::vector<std::vector<int>>& momenta) const {
+    if (momenta.empty()) throw std::runtime_error("slice_gram: no momenta");
+    std::vector<int> n(4 * momenta.size(), 0);
+    for (size_t p = 0; p < momenta.size(); ++p) {
+      if (momenta[p].size() > 4) throw std::runtime_error("slice_gram: a momentum has up to 4 components");
+      for (size_t mu = 0; mu < momenta[p].size(); ++mu) n[4 * p + mu] = momenta[p][mu];
+    }
+    return slice_gram_call(rhs, dir, static_cast<int>(momenta.size()), n.data());
+  }
   // this <- this + rhs * rhs_multiplier (:70-77)
   block_fermion_field& add(const block_fermion_field& rhs, double rhs_multiplier) {
     dev2(rhs);
@@ -321,6 +338,18 @@ class block_fermion_field {
       blockcg::check(bcg_field_download(f_, reinterpret_cast<double*>(host_.data())), lat_->ctx(), "download");
       host_valid_ = true;
     }
+  }
+  std::vector<block_matrix<N_rhs>> slice_gram_call(const block_fermion_field& rhs, int dir, int n_mom, const int* momenta) const {
+    if (dir < 0 || dir >= static_cast<int>(lat_->dims().size())) throw std::runtime_error("slice_gram: direction outside the lattice");
+    flush();
+    rhs.flush();
+    const size_t n = static_cast<size_t>(n_mom > 0 ? n_mom : 1) * lat_->dims()[dir], mm = static_cast<size_t>(N_rhs) * N_rhs;
+    std::vector<std::complex<double>> buf(n * mm);
+    blockcg::check(bcg_field_slice_gram(f_, rhs.f_, dir, n_mom, momenta, reinterpret_cast<double*>(buf.data())), lat_->ctx(),
+                   "slice_gram");
+    std::vector<block_matrix<N_rhs>> out(n);
+    for (size_t k = 0; k < n; ++k) std::copy(buf.begin() + k * mm, buf.begin() + (k + 1) * mm, out[k].data());  // column-major both
+    return out;
   }
   void noise(int kind, unsigned long long seed) {
     blockcg::check(bcg_field_fill_noise(f_, kind, seed), lat_->ctx(), "fill_noise");

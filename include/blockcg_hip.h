@@ -344,6 +344,22 @@ int bcg_field_set_wall_sources(bcg_field* f, int dir, const int* slice, const in
  * BCG_ERR_INVALID: mixed widths, parities or contexts, dir outside 0 .. ndim-1; BCG_ERR_UNSUPPORTED: more than 2^20 / m
  * slices.  Synchronizes the stream. */
 int bcg_field_slice_dot(const bcg_field* a, const bcg_field* b, int dir, double* out);
+/* Per-slice Gram matrices with momentum projection: all column pairs of bcg_field_hermitian_dot resolved by slice,
+ *   out[((p*L_dir + t)*m + j)*m + i] = sum_{x: x_dir = t} w_p(x) sum_c conj(a[x,c,i]) b[x,c,j],
+ *   w_p(x) = exp(-2 pi i sum_{mu != dir} n_{p,mu} x_mu / L_mu),      n_{p,mu} = momenta[4*p + mu],
+ * interleaved (re, im); t, x_mu and L_mu are GLOBAL coordinates and extents, each (p, t) block an m x m matrix, column-major.
+ * n_mom = 0 (momenta may be NULL): the single momentum 0, no phase arithmetic at all.  Momenta are any integers, reduced
+ * mod L_mu exactly; the phase of a site is the product over ascending mu of entries exp(-2 pi i ((n_mu x_mu) mod L_mu) / L_mu)
+ * of per-direction tables computed on the host in double precision, so no value depends on the process grid.
+ * Summed over all ranks (one bcg_comm.allreduce_sum per chunk of momenta) and identical on every rank; the same bits on
+ * every call (a launch plan fixed by shape, width, parity, dir and n_mom; block sums added in a fixed order; no atomics).
+ * Full and half fields (both operands of one parity; the sites held contribute), every width 1..32; a == b reads the field
+ * once; a and b are not written.  Uses the context's existing scratch only.
+ * BCG_ERR_INVALID: mixed widths, parities or contexts, dir outside 0 .. ndim-1, n_mom < 0, n_mom > 0 with momenta == NULL,
+ * out == NULL, a non-zero momentum component along dir or along a direction >= ndim; BCG_ERR_UNSUPPORTED: the L_dir m^2
+ * entries of one momentum do not fit the scratch (2^20 entries); BCG_ERR_COMM: a divided lattice without a bcg_comm.  A
+ * failed call leaves out untouched.  Synchronizes the stream. */
+int bcg_field_slice_gram(const bcg_field* a, const bcg_field* b, int dir, int n_mom, const int* momenta, double* out);
 
 #ifdef __cplusplus
 }
