@@ -7,4 +7,5 @@ drop-in headers live in blockcg_amd/include/blockcg/.
 from ._lib import build, load, LIB_PATH  # noqa: F401
 from .api import (BlockCGError, Context, block_fermion_field, dirac_op, SBCGrQ, SBCGrQState, SUPPORTED_WIDTHS, true_residuals,
                   CG, SCG, BCG, BCGrQ, SBCGrQ_half_volume, SBCGrQ_sum, SBCGrQSumState,
-                  gauge_field, fermion_force, NOISE_GAUSSIAN, NOISE_Z2, NOISE_Z4)  # noqa: F401
+                  gauge_field, fermion_force, NOISE_GAUSSIAN, NOISE_Z2, NOISE_Z4,
+                  shift_sum, covariant_shift, laplacian, smear)  # noqa: F401

@@ -124,6 +124,10 @@ SIGNATURES = {
     "bcg_field_set_wall_sources": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_int_p, c_int_p, ctypes.c_int]),
     "bcg_field_slice_dot": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, c_dbl_p]),
     "bcg_field_slice_gram": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_int_p, c_dbl_p]),
+    "bcg_dirac_shift_sum": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_dbl_p, c_dbl_p,
+                                           c_dbl_p, ctypes.c_int]),
+    "bcg_covariant_smear": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                           ctypes.c_double, ctypes.c_int]),
 }
 
 _lib = None

@@ -440,6 +440,68 @@ def fermion_force(F, X, D, residues, scale=1.0, project=False, work=None):
     return F
 
 
+def _coefficients(v, ndim):
+    """None, one complex number for every direction, or one per direction -> ndim x (re, im) doubles (None stays None)."""
+    if v is None:
+        return None
+    a = np.asarray(v, dtype=np.complex128)
+    if a.ndim == 0:
+        a = np.full(ndim, complex(a))
+    if a.shape != (ndim,):
+        raise ValueError(f"expected one coefficient, or one per direction ({ndim})")
+    return np.ascontiguousarray(a).view(np.float64)
+
+
+def shift_sum(out, inp, links, c0=0.0, fwd=None, bwd=None, eta=False):
+    """out(x) = c0 inp(x) + sum_mu s_mu(x) [fwd[mu] U_mu(x) inp(x+mu) + bwd[mu] U_mu(x-mu)^dagger inp(x-mu)]
+    (include/blockcg_hip.h, bcg_dirac_shift_sum).  links: a dirac_op or a gauge_field.  c0, fwd[mu], bwd[mu] complex; fwd and
+    bwd one number per direction, one for all, or None (all 0); s_mu = eta_mu when eta, else 1.  A term whose coefficient is
+    exactly 0 is not evaluated.  Half fields: inp of parity p, out of parity 1 - p, c0 = 0."""
+    ctx = links.ctx
+    c = np.array([complex(c0)], dtype=np.complex128).view(np.float64)
+    f, b = _coefficients(fwd, ctx.ndim), _coefficients(bwd, ctx.ndim)
+    ctx.check(ctx.lib.bcg_dirac_shift_sum(ctx.h, links.h, out.h, inp.h, _dp(c), None if f is None else _dp(f),
+                                          None if b is None else _dp(b), 1 if eta else 0))
+    return out
+
+
+def covariant_shift(out, inp, links, mu, sign=+1):
+    """sign > 0: out(x) = U_mu(x) inp(x+mu);  sign < 0: out(x) = U_mu(x-mu)^dagger inp(x-mu).  Only direction mu's links and
+    that one neighbour row are read."""
+    ndim = links.ctx.ndim
+    if not 0 <= int(mu) < ndim or sign == 0:
+        raise ValueError("mu must be a direction of the lattice and sign non-zero")
+    one = np.zeros(ndim, dtype=np.complex128)
+    one[int(mu)] = 1.0
+    return shift_sum(out, inp, links, 0.0, one if sign > 0 else None, one if sign < 0 else None)
+
+
+def _but(ndim, dir, value):
+    if not -1 <= int(dir) < ndim:
+        raise ValueError(f"dir must be -1 or a direction of the lattice, got {dir}")
+    v = np.full(ndim, value, dtype=np.complex128)
+    if dir >= 0:
+        v[int(dir)] = 0.0
+    return v, ndim - (1 if dir >= 0 else 0)
+
+
+def laplacian(out, inp, links, dir=-1):
+    """out = sum_{mu != dir} [U_mu(x) inp(x+mu) + U_mu(x-mu)^dagger inp(x-mu) - 2 inp(x)]; dir = -1: every direction.
+    dir = 3 on a 4-D lattice is the spatial covariant Laplacian (its links of direction 3 are not read)."""
+    hop, n = _but(links.ctx.ndim, dir, 1.0)
+    return shift_sum(out, inp, links, -2.0 * n, hop, hop)
+
+
+def smear(f, links, dir, kappa, n_iter, work=None):
+    """f <- (1 + kappa Lap_dir)^n_iter f in place (include/blockcg_hip.h, bcg_covariant_smear): n_iter calls of shift_sum with
+    c0 = 1 - 2 kappa (number of smeared directions), fwd = bwd = kappa off dir, bit for bit.  work: a field of f's width
+    (None: allocated for the call); overwritten."""
+    ctx = links.ctx
+    ctx.check(ctx.lib.bcg_covariant_smear(ctx.h, links.h, f.h, None if work is None else work.h, int(dir), float(kappa),
+                                          int(n_iter)))
+    return f
+
+
 def _trace_buffers(trace_limit, S, m):
     if trace_limit <= 0:
         return None, None, None

@@ -4,6 +4,7 @@
 //   capi_solvers.hip    SBCGrQ (phases A / B / C, grouped and deferred updates), CG, SCG, BCG, BCGrQ, true residuals
 //   capi_force.hip      the fermion force of multi-shift solutions (bcg_force_accumulate), gauge-field download / zero
 //   capi_sources.hip    noise fields, point / wall sources, the slice-resolved inner product
+//   capi_shift.hip      the covariant nearest-neighbour sum with free coefficients, covariant smearing
 // Host code only; every loop over lattice sites is a HIP kernel (kernels_generic.hip, kernels_mfma.hip, kernels_stencil.hip).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -59,4 +59,6 @@ class dirac_op {
   std::shared_ptr<bcg_gauge> g_;
 };
 
+#include "shift.hpp"  // blockcg::shift_sum, covariant_shift, laplacian, smear (extensions)
+
 #endif

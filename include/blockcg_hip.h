@@ -361,6 +361,45 @@ int bcg_field_slice_dot(const bcg_field* a, const bcg_field* b, int dir, double*
  * failed call leaves out untouched.  Synchronizes the stream. */
 int bcg_field_slice_gram(const bcg_field* a, const bcg_field* b, int dir, int n_mom, const int* momenta, double* out);
 
+/* ---- covariant shifts, Laplacian and smearing (extensions) ---------------------------------------
+ * The nearest-neighbour sum with free coefficients,
+ *   out(x) = c0 in(x) + sum_mu s_mu(x) [ fwd[mu] U_mu(x) in(x+mu) + bwd[mu] U_mu(x-mu)^dagger in(x-mu) ],
+ * c0 = (re, im), fwd and bwd = ndim x (re, im) (NULL: all 0); s_mu(x) = eta_mu(x) = (-1)^(x_0+...+x_{mu-1}) in GLOBAL
+ * coordinates when eta != 0, and 1 otherwise.  Sites are periodic and links general complex 3 x 3, as everywhere here.
+ *  - Zero coefficients: a term whose coefficient is exactly 0 (re and im) is not evaluated.  A direction with
+ *    fwd[mu] == bwd[mu] == 0 reads neither its links nor its neighbour rows, so non-finite data in such links never reaches
+ *    out; c0 == 0 does not read in(x).
+ *  - A direction of extent 1 has the site itself as both neighbours (as in bcg_dirac_hop).
+ *  - With c0 = 0, fwd = 1/2, bwd = -1/2, eta = 1 the call is bcg_dirac_hop to rounding (not bit for bit).
+ *  - g: an operator's links or any link-shaped bcg_gauge of the context (e.g. smeared links uploaded with bcg_gauge_upload);
+ *    a stale gauge ghost is refreshed first, as by bcg_dirac_hop.
+ *  - Full fields: out and in distinct full fields of one width and context.  Half fields: in of parity p, out of parity
+ *    1 - p, c0 exactly 0; even extents and half ghost faces as for bcg_dirac_hop_half.
+ *  - Divided lattices: one blocking exchange of in's faces per call; every rank makes the same call; the argument checks
+ *    use global data only, so every rank returns the same status.
+ *  - BCG_ERR_INVALID: a NULL out, in, g or c0; out == in; mixed widths or contexts; wrong parities; a non-zero c0 with half
+ *    fields; a non-finite coefficient.  BCG_ERR_COMM: a divided lattice without a bcg_comm.  The arguments are checked
+ *    before the first launch or exchange: a call that fails them leaves out as it was (a BCG_ERR_HIP or BCG_ERR_COMM from
+ *    the exchange or the launch itself leaves out undefined).
+ *  - Profile key "shift_sum": 2 * 48 m bytes per site of out plus 144 bytes per site and direction with a non-zero
+ *    coefficient, and the flops of the terms evaluated ("shift_form_tile" / "shift_form_generic" count the kernel form). */
+int bcg_dirac_shift_sum(bcg_context* ctx, const bcg_gauge* g, bcg_field* out, const bcg_field* in,
+                        const double* c0 /* (re, im) */, const double* fwd /* ndim x (re, im), NULL = all 0 */,
+                        const double* bwd /* likewise */, int eta);
+/* f <- (1 + kappa * Lap_dir)^n_iter f,  Lap_dir psi = sum_{mu != dir} [U psi(x+mu) + U^dagger psi(x-mu) - 2 psi];
+ * dir = -1: every direction.  Exactly n_iter calls of bcg_dirac_shift_sum with c0 = 1 - 2 kappa (number of smeared
+ * directions), fwd = bwd = kappa on the smeared directions, 0 on dir, eta = 0, alternating between f and work; the result
+ * ends in f (after an odd number of steps by a device copy) and is bit-identical to the same calls made by hand.
+ * work: a field of f's width (NULL: allocated for the call); contents undefined afterwards.  n_iter = 0 leaves f untouched.
+ * Full fields only: a half field returns BCG_ERR_UNSUPPORTED, because one link flips the parity.  "smear" is no profile key
+ * of its own: the steps are timed as "shift_sum".
+ * BCG_ERR_INVALID: a NULL g or f; mixed contexts; dir outside -1 .. ndim-1; n_iter < 0; a non-finite kappa; work == f; a
+ * work of another width or parity.  BCG_ERR_COMM: a divided lattice without a bcg_comm.  These are checked before the first
+ * launch or exchange, and a call that fails them leaves f as it was.  A BCG_ERR_HIP or BCG_ERR_COMM from a launch or an
+ * exchange part-way through the steps leaves the contents of f (and of work) undefined. */
+int bcg_covariant_smear(bcg_context* ctx, const bcg_gauge* g, bcg_field* f, bcg_field* work, int dir, double kappa,
+                        int n_iter);
+
 #ifdef __cplusplus
 }
 #endif
