@@ -390,6 +390,7 @@ int bcg_context_create(bcg_context** out, int device, void* stream, int ndim, co
   if (const char* e = std::getenv("BCG_ROW_BLOCKS_B")) c->row_blocks_B = std::atoi(e);
   if (const char* e = std::getenv("BCG_ROW_BLOCKS_C")) c->row_blocks_C = std::atoi(e);
   if (const char* e = std::getenv("BCG_ROW_BATCHED")) c->row_batched = std::atoi(e) != 0;
+  if (const char* e = std::getenv("BCG_HOP_FACTORED")) c->hop_factored = std::atoi(e) != 0;
   if (const char* e = std::getenv("BCG_HOP_WALK")) c->hop_tune.patch_walk = std::atoi(e) != 0;
   if (const char* e = std::getenv("BCG_HOP_BLOCKS")) c->hop_tune.blocks = std::atoi(e);
   if (const char* e = std::getenv("BCG_HOP_BLOCKS_OVERLAP")) c->hop_tune.blocks_overlap = std::atoi(e);
@@ -509,6 +510,14 @@ int bcg_debug_read_scratch(bcg_context* c, void* host, size_t bytes) {
   if (!c || !host || !c->partials || bytes > c->partials_bytes) return BCG_ERR_INVALID;
   BCG_TRY(stream_sync(c));
   HIP_TRY(c, hipMemcpy(host, c->partials, bytes, hipMemcpyDeviceToHost));
+  return BCG_OK;
+}
+
+// Test aid, like bcg_debug_read_scratch not part of the header: the Gram matrix G = P_0^dagger (A + sigma_0) P_0 of the last
+// phase A of a solver on this context, as the host used it (m x m complex, column-major, interleaved re / im)
+int bcg_debug_phase_a_gram(const bcg_context* c, int m, double* out) {
+  if (!c || !out || m <= 0 || c->phaseA_gram.dim() != m) return BCG_ERR_INVALID;
+  c->phaseA_gram.store(out);
   return BCG_OK;
 }
 

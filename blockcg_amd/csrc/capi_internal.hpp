@@ -70,6 +70,7 @@ struct ProfScope {
   bcg_context* c;
   bcg::ProfEntry* e = nullptr;
   hipEvent_t a = nullptr, b = nullptr;
+  double booked_bytes = 0.0, booked_flops = 0.0;
   // alg_bytes: the ALGORITHMIC HBM bytes of what is launched inside the scope (per-site figure x the
   // sites this launch processes); summed per kernel class so that bench.py's roofline is right for split launches
   // (phase C in two launches, capacity-mode windows) too.
@@ -80,9 +81,20 @@ struct ProfScope {
     e = &c->prof[name];
     e->bytes += alg_bytes;
     e->flops += alg_flops;
+    booked_bytes = alg_bytes;
+    booked_flops = alg_flops;
     a = take();
     b = take();
     (void)hipEventRecord(a, c->stream);
+  }
+  // nothing was launched inside the scope after all (a launcher declined): book nothing, count nothing
+  void cancel() {
+    if (!e) return;
+    e->bytes -= booked_bytes;
+    e->flops -= booked_flops;
+    c->event_pool.push_back(a);
+    c->event_pool.push_back(b);
+    e = nullptr;
   }
   ~ProfScope() {
     if (!e) return;
@@ -106,6 +118,11 @@ constexpr size_t kMatSlotBytes = 32 * 32 * sizeof(double2);
 constexpr int kMatSlots = 96;
 
 constexpr int kFastBlocks = 1024;  // persistent-style grids: 4 blocks per CU
+// stamps builds (-DBCG_HOP4B_STAMPS): a stencil kernel with a Gram product leaves its stamps behind the partials of the
+// largest grid, inside the partials buffer (kMaxGramBlocks slots of 32 x 32: ensure_scratch)
+static_assert(bcg::kHopStampsSkipBlocks == kFastBlocks &&
+                  static_cast<size_t>(bcg::kHopStampsSkipBlocks) * (32 * 32 * 16 + 4 * 16 * 8) <= static_cast<size_t>(kMaxGramBlocks) * 32 * 32 * 16,
+              "stamps of the Gram forms (4 waves x 16 doubles per block): behind the largest grid's partials, inside the buffer");
 
 inline int64_t rows_of(const bcg_field* f) { return f->sites * 3; }
 // algorithmic bytes: `fields` passes over a width-m field (s = 48 m bytes per site) plus `links` passes over the gauge
@@ -170,8 +187,10 @@ inline bool ring_overlapped(const bcg_context* c) { return c->ring_overlap && ca
 // The device memory apply_shifted needs for operands shaped like `like`, allocated now rather than at the first call
 int reserve_operator_scratch(bcg_context* c, const bcg_field* like);
 // T = (mass^2 + sigma0) P - D(D(P))   [op + add(P, sigma0), inc/block_solvers.hpp:134-136]
+// gram_self: set when the partials are those of a self-product W^dagger W (the factored pair), whose diagonal is real;
+// phase_A (capi_solvers.hip) is its only consumer
 int apply_shifted(bcg_context* c, const bcg_gauge* g, double mass, double sigma0, bcg_field* T, const bcg_field* P,
-                  int* gram_blocks = nullptr, bool* gram_folded = nullptr);
+                  int* gram_blocks = nullptr, bool* gram_folded = nullptr, bool* gram_self = nullptr);
 
 // ---- capi_solvers.hip ------------------------------------------------------------------------------
 int pair_shifts_depth(const bcg_context* c, int m, int n_shifts);

@@ -553,10 +553,32 @@ int reserve_operator_scratch(bcg_context* c, const bcg_field* like) {
   return BCG_OK;
 }
 
+// Phase A of a solver (T and G = P^dagger T wanted together) on whole full-volume fields at m = 16, both launches on the
+// bundle sweep of an undivided lattice: A + sigma0 = mu^2 - D^2 = (mu + D)(mu - D) with mu = sqrt(mass^2 + sigma0), D
+// anti-Hermitian for any links.  W = (mu - D) P, T = (mu + D) W, G = P^dagger T = W^dagger W: neither pass reads a field
+// other than its stencil input (the second pass of the other form reads P besides: a third of its traffic), and G is a
+// self-product.  Everything else -- bcg_dirac_apply, true residuals, capacity mode, half fields, other widths, divided
+// lattices, the row form of the sweep -- keeps the other form's kernels.  BCG_HOP_FACTORED=0 (read at context creation)
+// switches it off.  DESIGN.md section 4.
+static bool factored_pair(const bcg_context* c, int m, double c0, bool want_gram) {
+  if (!c->hop_factored || !want_gram || m != 16 || !(c0 > 0.0) || c->distributed || c->force_tile_classes || !fast_hop(c, m))
+    return false;  // (distributed: some direction is divided over ranks)
+  return bcg::hop_uses_bundle(m, c->lat, kFastBlocks, c->hop_tune, 0, bcg::HopWindow(), /*plain=*/true) &&
+         bcg::hop_uses_bundle(m, c->lat, kFastBlocks, c->hop_tune, 0, bcg::HopWindow(), /*plain=*/false);
+}
+
+// whole full-volume fields as the reference writes it: tmp = D P, T = (mass^2 + sigma0) P - D tmp (with P^dagger T where asked)
+static int apply_unfactored(bcg_context* c, const bcg_gauge* g, double mass, double sigma0, bcg_field* T, const bcg_field* P,
+                            bcg_field* tmp, int* gram_blocks, bool* gram_folded) {
+  BCG_TRY(hop(c, g, tmp, P, bcg::HOP_PLAIN, nullptr, 0.0));
+  return hop(c, g, T, tmp, bcg::HOP_SHIFTED, P, mass * mass + sigma0, gram_blocks, gram_folded);
+}
+
 // T = (mass^2 + sigma0) P - D(D(P))   [op + add(P, sigma0), inc/block_solvers.hpp:134-136]
 int apply_shifted(bcg_context* c, const bcg_gauge* g, double mass, double sigma0, bcg_field* T, const bcg_field* P,
-                  int* gram_blocks, bool* gram_folded) {
+                  int* gram_blocks, bool* gram_folded, bool* gram_self) {
   if (gram_folded) *gram_folded = false;
+  if (gram_self) *gram_self = false;
   if (P->parity >= 0) {  // A restricted to one parity: tmp (other parity) = D P, T = (mass^2 + sigma0) P - D tmp
     if (gram_blocks) *gram_blocks = 0;
     if (T->parity != P->parity) BCG_FAIL(c, BCG_ERR_INVALID, "half-volume operator: result and argument must have the same parity");
@@ -651,8 +673,42 @@ int apply_shifted(bcg_context* c, const bcg_gauge* g, double mass, double sigma0
   if (capacity_path(c, P->m)) return apply_shifted_ring(c, g, mass, sigma0, T, P, gram_blocks);
   bcg_field* tmp;
   BCG_TRY(get_tmp(c, P->m, &tmp));
-  BCG_TRY(hop(c, g, tmp, P, bcg::HOP_PLAIN, nullptr, 0.0));
-  return hop(c, g, T, tmp, bcg::HOP_SHIFTED, P, mass * mass + sigma0, gram_blocks, gram_folded);
+  if (factored_pair(c, P->m, mass * mass + sigma0, gram_blocks != nullptr)) {
+    // mu * mu differs from mass^2 + sigma0 by at most one ulp: a perturbation of sigma0 by 1e-16 (mass^2 + sigma0), about
+    // 1e-22 at mass 1e-3 -- far below the rounding of the operator itself (1e-16 |D^2 P|, |D^2| up to 16)
+    const double mu = std::sqrt(mass * mass + sigma0);
+    BCG_TRY(halo_gauge(c, const_cast<bcg_gauge*>(g)));
+    BCG_TRY(ensure_scratch(c));
+    bcg::HopTuning tune = c->hop_tune;
+    int nb1;
+    {  // W = (mu - D) P: the plain hop's streams
+      ProfScope ps(c, "hop", alg_bytes(c, P->m, 2, 1), hop_flops(c, P->m, false));
+      nb1 = bcg::launch_hop_fast(c->stream, P->m, c->lat, g->U, g->Ughost, P->d, c->halo_recv, tmp->d, bcg::HOP_FACT1, nullptr, mu,
+                                 c->partials, false, kFastBlocks, tune, 0);
+      if (nb1 < 0) ps.cancel();
+    }
+    // the launcher declined where factored_pair() expected it to accept: nothing has run, the other form below serves
+    if (nb1 < 0) return apply_unfactored(c, g, mass, sigma0, T, P, tmp, gram_blocks, gram_folded);
+    if (c->profiling) c->prof["stencil_form_factored_pair"].count += 1;
+    note_stencil_form(c, P->m, 0, bcg::HopWindow(), /*plain=*/true);
+    BCG_TRY(check_launch(c, "hop"));
+    // T = (mu + D) W and the partials of W^dagger W = P^dagger T; tmp (= W) is read by this launch alone
+    const bool fold = gram_folded && bcg::hop_folds_gram(P->m, c->lat, kFastBlocks, tune, bcg::HopWindow());
+    if (fold) tune.fold = bcg::GramFold{c->dev_gram, c->fold_tickets};
+    int nb;
+    {
+      note_stencil_form(c, P->m, 0, bcg::HopWindow());
+      ProfScope ps(c, "hop_shifted_gram", alg_bytes(c, P->m, 2, 1), hop_flops(c, P->m, true));
+      nb = bcg::launch_hop_fast(c->stream, P->m, c->lat, g->U, g->Ughost, tmp->d, c->halo_recv, T->d, bcg::HOP_FACT2, nullptr, mu,
+                                c->partials, true, kFastBlocks, tune, 0);
+    }
+    if (nb < 0) BCG_FAIL(c, BCG_ERR_UNSUPPORTED, "factored stencil pair: second factor rejected after the first ran");
+    *gram_blocks = nb;
+    if (fold) *gram_folded = true;
+    if (gram_self) *gram_self = true;
+    return check_launch(c, "hop_shifted_gram");
+  }
+  return apply_unfactored(c, g, mass, sigma0, T, P, tmp, gram_blocks, gram_folded);
 }
 
 

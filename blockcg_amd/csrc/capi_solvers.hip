@@ -8,10 +8,20 @@ namespace bcg_impl {
 // Phase A of an iteration: T = (A + sigma0) P ; G = P^dagger T   (:134-140)
 int phase_A(bcg_context* c, const bcg_gauge* g, double mass, double sigma0, bcg_field* T, const bcg_field* P, CMat& G) {
   int nb = 0;
-  bool folded = false;
-  BCG_TRY(apply_shifted(c, g, mass, sigma0, T, P, &nb, &folded));
-  if (nb > 0) return finish_gram(c, P->m, nb, G, true, folded);
-  return gram(c, P, T, G);
+  bool folded = false, self = false;
+  BCG_TRY(apply_shifted(c, g, mass, sigma0, T, P, &nb, &folded, &self));
+  if (nb > 0) {
+    BCG_TRY(finish_gram(c, P->m, nb, G, true, folded));
+    // a self-product's diagonal is a sum of squares: what the kernel leaves in its imaginary part is the rounding of
+    // x y - y x in the matrix pipe, not a value
+    if (self)
+      for (int i = 0; i < P->m; ++i) G(i, i) = G(i, i).real();
+    c->phaseA_gram = G;
+    return BCG_OK;
+  }
+  BCG_TRY(gram(c, P, T, G));
+  c->phaseA_gram = G;
+  return BCG_OK;
 }
 
 // Phase B: Q -= T alpha ; G2 = Q^dagger Q   (:148 and the Gram half of :152)

@@ -57,6 +57,8 @@ struct bcg_context {
   int row_blocks_B = 1024, row_blocks_C = 1024;  // persistent grids of the fused row kernels (phase B, phase C)
   bool row_batched = true;  // m = 16: phase B, k_phaseC_p0 and K5 / K6 batch their stores through LDS (BCG_ROW_BATCHED=0: the plain kernels)
   bcg::HopTuning hop_tune;  // specialised stencil: tile walk, patch shape, grid, streaming hints
+  bcg::CMat phaseA_gram;     // the last G = P^dagger (A + sigma0) P of a solver's phase A, as the host used it (bcg_debug_phase_a_gram)
+  bool hop_factored = true;  // phase A at m = 16: A + sigma0 as the factored stencil pair (apply_shifted; BCG_HOP_FACTORED=0: off)
 
   // scratch
   std::map<int, bcg_field*> tmp_field;   // per width: the `tmp` of dirac_op::op (inc/dirac_op.hpp:39); key m + 1000 (1 + parity)

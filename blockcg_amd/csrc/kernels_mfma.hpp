@@ -66,6 +66,10 @@ struct HopSync {
                                  // 20 % fewer bytes past the L2 (45.7 vs 57.2 GB, 59.0 vs 72.0 GB); window 3 costs 2 %
 };
 
+// Stamps builds (-DBCG_HOP4B_STAMPS; tools/hop_stamps.py fact2, which carries the same number): the stencil forms with a Gram
+// product write their stamps this many blocks' partials (m x m complex each) behind the start of the partials buffer
+constexpr int kHopStampsSkipBlocks = 1024;
+
 // Tuning of the specialised 4-D stencil (defaults chosen by measurement at 64^4, m = 16).
 struct HopTuning {
   bool patch_walk = true;        // per-XCD patches swept along x3 (false: lexicographic tile order)

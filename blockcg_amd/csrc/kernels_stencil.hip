@@ -949,6 +949,16 @@ __device__ __forceinline__ void hop4b_body(const LatticeDev& lat, const double2*
   constexpr bool RING_IN = RING && MODE == HOP_SHIFTED;
   constexpr bool RESID = MODE == HOP_RESID;  // no output: the Gram product of (c0 p - D in - b) with itself, b passed as `out`
   static_assert(!RESID || (GRAM && !RING), "the residual form accumulates a Gram product and is not ring-addressed");
+  // The factored pair (kernels.hpp: HOP_FACT1, HOP_FACT2).  The shift term multiplies the stencil's own input, and the own
+  // row of every site is in the wave's row slot of the current slice (the one that serves the x0 neighbours): no `p`.  Two
+  // separate questions from here on, so that the memory pipeline of these modes cannot drift from the plain form's:
+  //   HAS_P  -- a global `p` is read (loads, addresses, the wait counts of the pipelined step);
+  //   SHIFT  -- the epilogue has a c0 term (from `p`, or from the own row).
+  constexpr bool FACT = MODE == HOP_FACT1 || MODE == HOP_FACT2;
+  constexpr bool HAS_P = MODE == HOP_SHIFTED || MODE == HOP_RESID;
+  constexpr bool SHIFT = HAS_P || FACT;
+  static_assert(!FACT || (M == 16 && !RING && !CB), "factored pair: whole full-volume fields at m = 16");
+  static_assert(!FACT || GRAM == (MODE == HOP_FACT2), "factored pair: the second factor carries the Gram product");
   // CB (checkerboard, half-volume fields -- kernels_generic.hip "Half-volume fields"): `in` holds the sites of one parity,
   // `out` / `p` those of the other, both in the compact order, and `lat` is the COMPACT lattice (L[0] = half the row).  A
   // row (x1, x2, x3) of the output has r = (x1 + x2 + x3 + parity of out) & 1 and its compact site k is x0 = 2 k + r; the
@@ -1455,11 +1465,11 @@ __device__ __forceinline__ void hop4b_body(const LatticeDev& lat, const double2*
         asm volatile("" : "+v"(q1[0]), "+v"(q1[1]), "+v"(q1[2]), "+v"(q2[0]), "+v"(q2[1]), "+v"(q2[2]));
       }
       constexpr int nB = 3 + 2 * NHD;                               // row DMAs
-      constexpr int nE = MODE == HOP_PLAIN ? 0 : 3;                 // p
+      constexpr int nE = HAS_P ? 3 : 0;                             // p (the factored pair reads none: the plain form's counts)
       // link DMAs of this wave (checkerboard form: the forward links and all four directions' backward links, every wave)
       const int nC = CB ? RFW + 4 * RBK : RFW + 1 + (e1 ? 0 : RBK) + (e2 ? 0 : RBK);
       constexpr int nD = 6, nS = 3;
-      constexpr int SPREAD = MODE == HOP_PLAIN ? 0 : BCG_HOP4B_SPREAD;  // 1: rows, 2: links, 4: second next-row group
+      constexpr int SPREAD = HAS_P ? BCG_HOP4B_SPREAD : 0;  // 1: rows, 2: links, 4: second next-row group
       constexpr bool SP_B = (SPREAD & 1) != 0, SP_C = (SPREAD & 2) != 0, SP_D = (SPREAD & 4) != 0;
       (void)nB;
       for (int x3 = win.x3_lo; x3 < x3_end; ++x3) {
@@ -1549,6 +1559,12 @@ __device__ __forceinline__ void hop4b_body(const LatticeDev& lat, const double2*
         for (int c = 0; c < 3; ++c) {
           f0[c] = Cown[co + (CB ? rr : 1) * 3 * M + c * M];      // CB: input sites k + rr and k - 1 + rr
           b0[c] = Cown[co + (CB ? rr - 1 : -1) * 3 * M + c * M];
+        }
+        // factored pair: the lane's own site, from the same slot (nothing writes it during the step: the +x3 DMA goes to Cn)
+        dv2 own[3];
+        if (FACT) {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) own[c] = Cown[co + c * M];
         }
         const int64_t crow_site = static_cast<int64_t>(col) + static_cast<int64_t>(x3) * S3;
         const char* const prow = INCR ? ip_p : reinterpret_cast<const char*>(p) + crow_site * RB;
@@ -1662,7 +1678,7 @@ __device__ __forceinline__ void hop4b_body(const LatticeDev& lat, const double2*
 #undef BCG_ROW_PIECE
         BCG_STAMPB(3)   // direction 0
         // ---- E: p;  C: links of slice x3 + 1 -> the other image (the INCR form in three pieces: forward 1, forward 2, the rest)
-        if (MODE != HOP_PLAIN) {
+        if (HAS_P) {
           asm volatile("; ASYNC_ISSUE p");
           pv[0] = ld_sv_async<0>(prow, voff);
           pv[1] = ld_sv_async<M * 16>(prow, voff);
@@ -1770,7 +1786,7 @@ __device__ __forceinline__ void hop4b_body(const LatticeDev& lat, const double2*
         BCG_STAMPB(9)   // direction 3
         if (more && !CB) park_u3(x3 + 1);  // U_3(x - 3) of the next slice = U_3 of this one (ds_read / ds_write; the DMAs fill the rest)
         double2 tv[3], pw[3];
-        if (MODE != HOP_PLAIN) {
+        if (HAS_P) {
           wait_vmcnt(more ? nC + nD : 0);  // p
           // The values are handed to hipcc as NEW registers written behind the wait (plain inputs, early-clobber outputs): with
           // the loaded registers as in-out operands of an empty asm the allocator may pick other registers for the operand
@@ -1783,15 +1799,20 @@ __device__ __forceinline__ void hop4b_body(const LatticeDev& lat, const double2*
           pw[1] = make_double2(r1.x, r1.y);
           pw[2] = make_double2(r2.x, r2.y);
         }
+        if (FACT) {
+#pragma unroll
+          for (int r = 0; r < 3; ++r) pw[r] = make_double2(own[r].x, own[r].y);
+        }
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
-          if (MODE == HOP_PLAIN) tv[r] = make_double2(0.5 * acc[r].x, 0.5 * acc[r].y);
+          if (!SHIFT) tv[r] = make_double2(0.5 * acc[r].x, 0.5 * acc[r].y);
+          else if (MODE == HOP_FACT2) tv[r] = make_double2(fma(c0, pw[r].x, 0.5 * acc[r].x), fma(c0, pw[r].y, 0.5 * acc[r].y));
           else tv[r] = make_double2(fma(c0, pw[r].x, -0.5 * acc[r].x), fma(c0, pw[r].y, -0.5 * acc[r].y));
           st_nt(reinterpret_cast<double2*>(orow + voff + r * M * 16), tv[r]);
         }
         if (GRAM) {
 #pragma unroll
-          for (int r = 0; r < 3; ++r) gram_step<16>(G, &pw[r], &tv[r]);
+          for (int r = 0; r < 3; ++r) gram_step<16>(G, &pw[r], FACT ? &pw[r] : &tv[r]);  // FACT2: W^dagger W
         }
         BCG_STAMPB(10)  // U_3 carried, wait for p, output, stores
         // everything but the stores: the links and the next rows have landed before this wave reaches the barrier
@@ -1899,7 +1920,7 @@ __device__ __forceinline__ void hop4b_body(const LatticeDev& lat, const double2*
       if (INCR) ip_p += id_row;
       if (INCR_OUT) ip_o += id_row;
       double2 pv[3], bv[3];
-      if (MODE != HOP_PLAIN) {
+      if (HAS_P) {
 #pragma unroll
         for (int r = 0; r < 3; ++r) pv[r] = ld_nt(reinterpret_cast<const double2*>(prow + voff + r * M * 16));
       }
@@ -1918,6 +1939,10 @@ __device__ __forceinline__ void hop4b_body(const LatticeDev& lat, const double2*
         const dv2 a = Cown[co + (CB ? rr : 1) * 3 * M + c * M], b = Cown[co + (CB ? rr - 1 : -1) * 3 * M + c * M];
         f[0][c] = make_double2(a.x, a.y);
         bk[0][c] = make_double2(b.x, b.y);
+        if (FACT) {  // factored pair: the lane's own site stands in for p
+          const dv2 o = Cown[co + c * M];
+          pv[c] = make_double2(o.x, o.y);
+        }
       }
       // Directions 1, 2: one neighbour is the partner wave's row (LDS), the other the row that leaves the bundle (o1 / o2);
       // which is forward depends on the wave (e1, e2).  The two cases are two calls of the direction's arithmetic below,
@@ -2029,14 +2054,15 @@ __device__ __forceinline__ void hop4b_body(const LatticeDev& lat, const double2*
       double2 tv[3];
 #pragma unroll
       for (int r = 0; r < 3; ++r) {
-        if (MODE == HOP_PLAIN) tv[r] = make_double2(0.5 * acc[r].x, 0.5 * acc[r].y);
+        if (!SHIFT) tv[r] = make_double2(0.5 * acc[r].x, 0.5 * acc[r].y);
+        else if (MODE == HOP_FACT2) tv[r] = make_double2(fma(c0, pv[r].x, 0.5 * acc[r].x), fma(c0, pv[r].y, 0.5 * acc[r].y));
         else tv[r] = make_double2(fma(c0, pv[r].x, -0.5 * acc[r].x), fma(c0, pv[r].y, -0.5 * acc[r].y));
         if (RESID) tv[r] = make_double2(tv[r].x - bv[r].x, tv[r].y - bv[r].y);  // AX -= B (test/solvers.cpp:109)
         else st_nt(reinterpret_cast<double2*>(orow + voff + r * M * 16), tv[r]);
       }
       if (GRAM) {
 #pragma unroll
-        for (int r = 0; r < 3; ++r) gram_step<16>(G, RESID ? &tv[r] : &pv[r], &tv[r]);
+        for (int r = 0; r < 3; ++r) gram_step<16>(G, RESID ? &tv[r] : &pv[r], FACT ? &pv[r] : &tv[r]);  // FACT2: W^dagger W
       }
       if (hw.sync != nullptr && tid == 0 && step_n < hw.sync_stride)
         __hip_atomic_fetch_add(hw.sync + cls * hw.sync_stride + step_n, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -2052,8 +2078,9 @@ __device__ __forceinline__ void hop4b_body(const LatticeDev& lat, const double2*
     }
   }
 #ifdef BCG_HOP4B_STAMPS
-  if (!GRAM && lane == 0) {
-    double* o = reinterpret_cast<double*>(partials) + (static_cast<int64_t>(blockIdx.x) * 4 + wave) * 16;
+  // (the forms with a Gram product: behind the partials of the largest grid -- kHopStampsSkipBlocks; tools/hop_stamps.py fact2)
+  if ((!GRAM || FACT) && lane == 0) {
+    double* o = reinterpret_cast<double*>(partials) + (GRAM ? kHopStampsSkipBlocks * M * M * 2 : 0) + (static_cast<int64_t>(blockIdx.x) * 4 + wave) * 16;
     for (int i = 0; i < 16; ++i) o[i] = static_cast<double>(seg[i]);
   }
 #endif
@@ -2082,6 +2109,12 @@ template __global__ void k_hop4b<16, HOP_PLAIN, false, false>(LatticeDev, const 
 template __global__ void k_hop4b<16, HOP_SHIFTED, true, false>(LatticeDev, const double2*, const double2*, const double2*,
                                                                 const double2*, double2*, const double2*, double, double2*,
                                                                 HopWalk, HopWindow);
+template __global__ void k_hop4b<16, HOP_FACT1, false, false>(LatticeDev, const double2*, const double2*, const double2*,
+                                                               const double2*, double2*, const double2*, double, double2*,
+                                                               HopWalk, HopWindow);
+template __global__ void k_hop4b<16, HOP_FACT2, true, false>(LatticeDev, const double2*, const double2*, const double2*,
+                                                              const double2*, double2*, const double2*, double, double2*,
+                                                              HopWalk, HopWindow);
 template __global__ void k_hop4c<16, HOP_PLAIN, false, 0, false>(LatticeDev, const double2*, const double2*, const double2*,
                                                                   const double2*, double2*, const double2*, double, double2*,
                                                                   HopWalk, HopWindow);
@@ -2190,6 +2223,9 @@ static int launch_hop4(hipStream_t s, const LatticeDev& lat, const double2* U, c
   const size_t lds_g = gram ? sizeof(double) * 4 * 8 * 64 : 0;
   if (pl.list && grid == 0) return 0;  // no boundary tiles
   const int cls_t = pl.list ? 0 : cls;  // the list holds exactly the launch's tiles: no class filter in the kernel
+  // the factored pair exists in the bundle sweep only: whole full-volume fields at m = 16, FACT2 with its Gram product
+  const bool fact = mode == HOP_FACT1 || mode == HOP_FACT2;
+  if (fact && (M != 16 || win.cb || win.ring > 0 || cls != 0 || gram != (mode == HOP_FACT2))) return -1;
   // checkerboard form (half-volume fields): the bundle sweep at m = 16, 32 on a lattice whose direction 0 is not divided
   // over ranks (lat: the compact lattice, with the half ghost faces' offsets), or nothing (the caller then runs the generic
   // half-volume kernel)
@@ -2245,7 +2281,9 @@ static int launch_hop4(hipStream_t s, const LatticeDev& lat, const double2* U, c
     if (mode == HOP_RESID) {
       if (M != 16 || !gram || win.ring > 0) return -1;
       BCG_LAUNCH4B(16, HOP_RESID, true, false);
-    } else if (gram && M == 16 && mode == HOP_SHIFTED) BCG_LAUNCH4B_R(16, HOP_SHIFTED, true);
+    } else if (mode == HOP_FACT1) BCG_LAUNCH4B(16, HOP_FACT1, false, false);
+    else if (mode == HOP_FACT2) BCG_LAUNCH4B(16, HOP_FACT2, true, false);
+    else if (gram && M == 16 && mode == HOP_SHIFTED) BCG_LAUNCH4B_R(16, HOP_SHIFTED, true);
     else if (gram && M == 8 && mode == HOP_SHIFTED) BCG_LAUNCH4B_R(8, HOP_SHIFTED, true);
     else if (mode == HOP_PLAIN) BCG_LAUNCH4B_R(M, HOP_PLAIN, false);
     else BCG_LAUNCH4B_R(M, HOP_SHIFTED, false);
@@ -2253,7 +2291,7 @@ static int launch_hop4(hipStream_t s, const LatticeDev& lat, const double2* U, c
 #undef BCG_LAUNCH4B
     return grid;
   }
-  if (mode == HOP_RESID) return -1;  // the fused residual form exists in the bundle sweep only
+  if (mode == HOP_RESID || fact) return -1;  // the fused residual form and the factored pair exist in the bundle sweep only
   if (pl.column) {
     if (hw.sync) (void)hipMemsetAsync(hw.sync, 0, sizeof(unsigned) * 8 * hw.sync_stride, s);
     const size_t lds_u = sizeof(double2) * 2 * ((SPB + 1) * 36 + 3 * SPB * 9);

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Tuning aid (GPU box): where the cycles of a stencil tile go (plain form), from in-kernel s_memtime stamps.
 k_hop4c: library built with -DBCG_HOP4C_STAMPS and BCG_HOP_BUNDLE=0; k_hop4b (the default form): -DBCG_HOP4B_STAMPS and
-`python tools/hop_stamps.py 4b`  (tools/build_variant.sh stamps "-DBCG_HOP4B_STAMPS"; BCG_LIB=...)."""
+`python tools/hop_stamps.py 4b`  (tools/build_variant.sh stamps "-DBCG_HOP4B_STAMPS"; BCG_LIB=...); `pipe`: the same build, the
+segments of the software-pipelined step; `fact2`: the second pass of the factored pair (HOP_FACT2, with its Gram product) of the
+solver's phase A instead of the plain hop, which leaves its stamps behind the Gram partials."""
 import ctypes
 import os
 import sys
@@ -19,23 +21,28 @@ B = bc.block_fermion_field(ctx, m).setRandom(seed=2)
 X = [bc.block_fermion_field(ctx, m)]
 st = bc.SBCGrQState(X, B, D, [0.0], 0.0, 0.0, consume_B=False)
 st.iterate(1)  # allocates the scratch buffer
+mode = sys.argv[1] if len(sys.argv) > 1 else ""
 y = bc.block_fermion_field(ctx, m)
 for _ in range(3):
-    D.D(y, B)
+    if mode == "fact2":
+        st.iterate(1)
+    else:
+        D.D(y, B)
 ctx.synchronize()
 nblk = 512
-NSEG = 16 if len(sys.argv) > 1 and sys.argv[1] in ("4b", "pipe") else 8
-buf = np.zeros(nblk * 4 * NSEG, dtype=np.float64)
+NSEG = 16 if mode in ("4b", "pipe", "fact2") else 8
+skip = 1024 * m * m * 2 if mode == "fact2" else 0  # doubles: the Gram partials of the largest grid (kHopStampsSkipBlocks, kernels_mfma.hpp)
+buf = np.zeros(skip + nblk * 4 * NSEG, dtype=np.float64)
 lib = ctx.lib
 lib.bcg_debug_read_scratch.restype = ctypes.c_int
 lib.bcg_debug_read_scratch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t]
 assert lib.bcg_debug_read_scratch(ctx.h, buf.ctypes.data_as(ctypes.c_void_p), buf.nbytes) == 0
-seg = buf.reshape(nblk, 4, NSEG)
+seg = buf[skip:].reshape(nblk, 4, NSEG)
 tiles = 64 ** 4 // 16 // nblk
 names = ["park+pace", "barrier", "issue(links,dir0)", "dir0", "dir1", "dir2", "dir3(+x3)", "tail(p,store)"]
 if len(sys.argv) > 1 and sys.argv[1] == "4b":
     names = ["pace(thread 0)", "barrier", "issue(DMAs,loads)", "dir0 (LDS only)", "dir1 (+wait loads)", "dir2", "dir3", "tail(park,store)"]
-if len(sys.argv) > 1 and sys.argv[1] == "pipe":  # the software-pipelined step (PIPE in hop4b_body)
+if mode in ("pipe", "fact2"):  # the software-pipelined step (PIPE in hop4b_body)
     names = ["loop overhead", "barrier", "-x3 readback + row DMAs", "dir0", "issue p + link DMAs", "dir1", "issue next rows", "dir2",
              "WAIT +x3 row", "dir3", "carry U3, WAIT p, output, stores", "WAIT links + next rows"]
 tot = seg.sum(axis=2)
