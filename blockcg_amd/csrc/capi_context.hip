@@ -521,6 +521,14 @@ int bcg_debug_phase_a_gram(const bcg_context* c, int m, double* out) {
   return BCG_OK;
 }
 
+// Test aid: the same matrix as the device summed it, before the host mirrors the lower triangle and drops Im G_ii.  Set
+// only where a stencil kernel produced the partials (BCG_ERR_INVALID otherwise).
+int bcg_debug_phase_a_gram_raw(const bcg_context* c, int m, double* out) {
+  if (!c || !out || m <= 0 || c->phaseA_gram_raw.dim() != m) return BCG_ERR_INVALID;
+  c->phaseA_gram_raw.store(out);
+  return BCG_OK;
+}
+
 int bcg_context_stream(const bcg_context* c, void** stream_out, int* device_out) {
   if (!c) return BCG_ERR_INVALID;
   if (stream_out) *stream_out = c->stream;

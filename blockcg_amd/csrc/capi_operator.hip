@@ -692,7 +692,10 @@ int apply_shifted(bcg_context* c, const bcg_gauge* g, double mass, double sigma0
     if (c->profiling) c->prof["stencil_form_factored_pair"].count += 1;
     note_stencil_form(c, P->m, 0, bcg::HopWindow(), /*plain=*/true);
     BCG_TRY(check_launch(c, "hop"));
-    // T = (mu + D) W and the partials of W^dagger W = P^dagger T; tmp (= W) is read by this launch alone
+    // T = (mu + D) W and the partials of W^dagger W = P^dagger T; tmp (= W) is read by this launch alone.
+    // The kernel forms the self-product in two real products and stores Im G = C - C^T (mfma_common.hpp:
+    // gram_self_step): what it sums is Hermitian with a real diagonal already, so for this path finish_gram's mirror of the
+    // lower triangle and phase_A's drop of Im G_ii (gram_self below) change no bit.  They stay for the other forms.
     const bool fold = gram_folded && bcg::hop_folds_gram(P->m, c->lat, kFastBlocks, tune, bcg::HopWindow());
     if (fold) tune.fold = bcg::GramFold{c->dev_gram, c->fold_tickets};
     int nb;

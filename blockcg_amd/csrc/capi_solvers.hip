@@ -12,8 +12,12 @@ int phase_A(bcg_context* c, const bcg_gauge* g, double mass, double sigma0, bcg_
   BCG_TRY(apply_shifted(c, g, mass, sigma0, T, P, &nb, &folded, &self));
   if (nb > 0) {
     BCG_TRY(finish_gram(c, P->m, nb, G, true, folded));
-    // a self-product's diagonal is a sum of squares: what the kernel leaves in its imaginary part is the rounding of
-    // x y - y x in the matrix pipe, not a value
+    c->phaseA_gram_raw = CMat(P->m, c->pin_gram);  // (finish_gram has synchronised; test aid)
+    // a self-product's diagonal is a sum of squares: what gram_step leaves in its imaginary part is the rounding of
+    // x y - y x in the matrix pipe, not a value.  The factored pair's second factor now stores Im G = C - C^T
+    // (gram_self_block_store): its diagonal is exactly zero and its upper triangle exactly the conjugate of the lower, so
+    // this and finish_gram's mirror change nothing there.  Both stay: the four-product build of that kernel
+    // (-DBCG_SELF_GRAM_4M) and every other producer of partials still need them.
     if (self)
       for (int i = 0; i < P->m; ++i) G(i, i) = G(i, i).real();
     c->phaseA_gram = G;
@@ -21,6 +25,7 @@ int phase_A(bcg_context* c, const bcg_gauge* g, double mass, double sigma0, bcg_
   }
   BCG_TRY(gram(c, P, T, G));
   c->phaseA_gram = G;
+  c->phaseA_gram_raw = CMat();
   return BCG_OK;
 }
 

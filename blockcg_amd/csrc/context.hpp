@@ -58,6 +58,7 @@ struct bcg_context {
   bool row_batched = true;  // m = 16: phase B, k_phaseC_p0 and K5 / K6 batch their stores through LDS (BCG_ROW_BATCHED=0: the plain kernels)
   bcg::HopTuning hop_tune;  // specialised stencil: tile walk, patch shape, grid, streaming hints
   bcg::CMat phaseA_gram;     // the last G = P^dagger (A + sigma0) P of a solver's phase A, as the host used it (bcg_debug_phase_a_gram)
+  bcg::CMat phaseA_gram_raw; // the same as the device summed it, where a stencil kernel did: no mirror, no diagonal fix (bcg_debug_phase_a_gram_raw)
   bool hop_factored = true;  // phase A at m = 16: A + sigma0 as the factored stencil pair (apply_shifted; BCG_HOP_FACTORED=0: off)
 
   // scratch

@@ -959,6 +959,10 @@ __device__ __forceinline__ void hop4b_body(const LatticeDev& lat, const double2*
   constexpr bool SHIFT = HAS_P || FACT;
   static_assert(!FACT || (M == 16 && !RING && !CB), "factored pair: whole full-volume fields at m = 16");
   static_assert(!FACT || GRAM == (MODE == HOP_FACT2), "factored pair: the second factor carries the Gram product");
+  // The second factor's Gram product is W^dagger W, a block with itself: gram_self_step and gram_self_block_store
+  // (mfma_common.hpp), two matrix instructions per colour instead of four.  Only the matrix instructions of the tail and
+  // the final store differ; the vector-memory sequence and the wait counts are those of every other mode.
+  constexpr bool SELF_GRAM = MODE == HOP_FACT2 && kSelfGramProducts != 4;
   // CB (checkerboard, half-volume fields -- kernels_generic.hip "Half-volume fields"): `in` holds the sites of one parity,
   // `out` / `p` those of the other, both in the compact order, and `lat` is the COMPACT lattice (L[0] = half the row).  A
   // row (x1, x2, x3) of the output has r = (x1 + x2 + x3 + parity of out) & 1 and its compact site k is x0 = 2 k + r; the
@@ -1812,7 +1816,10 @@ __device__ __forceinline__ void hop4b_body(const LatticeDev& lat, const double2*
         }
         if (GRAM) {
 #pragma unroll
-          for (int r = 0; r < 3; ++r) gram_step<16>(G, &pw[r], FACT ? &pw[r] : &tv[r]);  // FACT2: W^dagger W
+          for (int r = 0; r < 3; ++r) {
+            if constexpr (SELF_GRAM) gram_self_step(G, &pw[r]);  // FACT2: W^dagger W as a self-product
+            else gram_step<16>(G, &pw[r], FACT ? &pw[r] : &tv[r]);
+          }
         }
         BCG_STAMPB(10)  // U_3 carried, wait for p, output, stores
         // everything but the stores: the links and the next rows have landed before this wave reaches the barrier
@@ -2062,7 +2069,10 @@ __device__ __forceinline__ void hop4b_body(const LatticeDev& lat, const double2*
       }
       if (GRAM) {
 #pragma unroll
-        for (int r = 0; r < 3; ++r) gram_step<16>(G, RESID ? &tv[r] : &pv[r], FACT ? &pv[r] : &tv[r]);  // FACT2: W^dagger W
+        for (int r = 0; r < 3; ++r) {
+          if constexpr (SELF_GRAM) gram_self_step(G, &pv[r]);  // FACT2: W^dagger W as a self-product
+          else gram_step<16>(G, RESID ? &tv[r] : &pv[r], FACT ? &pv[r] : &tv[r]);
+        }
       }
       if (hw.sync != nullptr && tid == 0 && step_n < hw.sync_stride)
         __hip_atomic_fetch_add(hw.sync + cls * hw.sync_stride + step_n, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -2087,6 +2097,7 @@ __device__ __forceinline__ void hop4b_body(const LatticeDev& lat, const double2*
 #undef BCG_STAMPB
   if (GRAM) {
     if (M == 8) gram_block_store_fold8<NW>(G, smem, partials, tid, hw.fold.out != nullptr);  // two sites per 16-lane row: see the fold
+    else if constexpr (SELF_GRAM) gram_self_block_store<NW>(G, smem, partials, tid, hw.fold.out != nullptr);
     else gram_block_store<16, NW>(G, smem, partials, tid, hw.fold.out != nullptr);
     gram_fold<M * M>(hw.fold, partials, tid, NW * 64);
   }

@@ -295,6 +295,34 @@ __device__ __forceinline__ void gram_step(GramAcc<M>& G, const double2* a, const
     }
 }
 
+// Self-product G = a^dagger a at M = 16 (the second factor of the factored stencil pair).  With x = Re a,
+// y = Im a:  Re G = x^T x + y^T y,  Im G = C - C^T with C = x^T y -- gram_step's fourth product is the transpose of its
+// third.  In every form G.im holds C alone and gram_self_block_store antisymmetrises it.
+// Three products (-DBCG_SELF_GRAM_3M, A/B builds): G.re exactly as gram_step(G, a, a) fills it, the same two instructions
+// in the same order.
+// Two products (the default; Gauss's trick as in rmul_acc): G.re holds P = (x + y)^T (x + y) = Re G + C + C^T and the
+// store forms Re G = P - (C + C^T).  One v_add_f64 per call for x + y.  Re G is then a difference of sums of comparable
+// size, |error| <= about 3 eps sqrt(G_ii G_jj) per entry where the direct sum has eps -- the size of the rounding the other
+// operator form and any other order of the site sum carry (measured: DESIGN.md §4, profiles/r08_self_gram_ab.txt).
+// -DBCG_SELF_GRAM_4M (A/B builds): the callers keep gram_step(G, a, a) and gram_block_store (kSelfGramProducts == 4).
+#if defined(BCG_SELF_GRAM_4M)
+constexpr int kSelfGramProducts = 4;
+#elif defined(BCG_SELF_GRAM_3M)
+constexpr int kSelfGramProducts = 3;
+#else
+constexpr int kSelfGramProducts = 2;
+#endif
+__device__ __forceinline__ void gram_self_step(GramAcc<16>& G, const double2* a) {
+  if constexpr (kSelfGramProducts == 2) {
+    const double s = a[0].x + a[0].y;
+    G.re[0] = mfma(s, s, G.re[0]);
+  } else {
+    G.re[0] = mfma(a[0].x, a[0].x, G.re[0]);
+    G.re[0] = mfma(a[0].y, a[0].y, G.re[0]);
+  }
+  G.im[0] = mfma(a[0].x, a[0].y, G.im[0]);
+}
+
 // Sum the per-wave fragments of a block in wave order and write partials[block][j*M + i].
 // red: LDS scratch of NW * JB*JB * 2 * 4 * 64 doubles.
 // wt: write-through (sc1) stores -- the partials are handed to another workgroup inside this launch (gram_fold)
@@ -330,6 +358,38 @@ __device__ __forceinline__ void gram_block_store(const GramAcc<M>& G, double* re
       const int i = 16 * (q / JB) + (l >> 4) + 4 * r, j = 16 * (q % JB) + (l & 15);
       st_partial(partials + static_cast<int64_t>(blockIdx.x) * (M * M) + j * M + i, make_double2(sr, si), wt);
     }
+  }
+}
+
+// gram_block_store for the accumulators of gram_self_step.  The fragments are summed in wave order as above; the thread
+// that writes element (i, j) also sums element (j, i) of C (fragment r' = j>>2, lane 16 (j&3) + i of the same buffer, in
+// the same wave order) and writes Im = C(i,j) - C(j,i): Im G_ii == 0 and G_ji == conj(G_ij) hold exactly in every block
+// partial (Re G(i,j) and Re G(j,i) are the same chain of the same products), and so in every sum of partials taken in a
+// fixed order -- the antisymmetrisation is linear, it commutes with gram_fold and reduce_partials.
+template <int NW>
+__device__ __forceinline__ void gram_self_block_store(const GramAcc<16>& G, double* red, double2* __restrict__ partials, int tid,
+                                                      bool wt = false) {
+  const int wave = tid >> 6, lane = tid & 63;
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    red[(wave * 8 + r) * 64 + lane] = G.re[0][r];
+    red[(wave * 8 + 4 + r) * 64 + lane] = G.im[0][r];
+  }
+  __syncthreads();
+  for (int e = tid; e < 4 * 64; e += NW * 64) {
+    const int l = e & 63, r = (e >> 6) & 3;
+    const int i = (l >> 4) + 4 * r, j = l & 15;
+    const int lt = 16 * (j & 3) + i, rt = j >> 2;  // element (j, i)
+    double sr = 0.0, c = 0.0, ct = 0.0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      sr += red[(w * 8 + r) * 64 + l];
+      c += red[(w * 8 + 4 + r) * 64 + l];
+      ct += red[(w * 8 + 4 + rt) * 64 + lt];
+    }
+    if constexpr (kSelfGramProducts == 2) sr -= c + ct;
+    st_partial(partials + static_cast<int64_t>(blockIdx.x) * 256 + j * 16 + i, make_double2(sr, c - ct), wt);
   }
 }
 
