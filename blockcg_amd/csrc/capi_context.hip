@@ -529,6 +529,17 @@ int bcg_debug_phase_a_gram_raw(const bcg_context* c, int m, double* out) {
   return BCG_OK;
 }
 
+// Test aid: one phase A of a solver on this context, T = (A + sigma_0) P with the Gram matrix P^dagger T behind it, by the
+// launches the solver's iteration takes (apply_shifted decides on the factored pair as it does there).  The matrix is read
+// with the two aids above.
+int bcg_debug_phase_a(bcg_context* c, const bcg_gauge* g, double mass, double sigma0, bcg_field* T, const bcg_field* P) {
+  DeviceScope on_device(c);
+  if (!c || !g || !same_shape(T, P) || T == P || g->ctx != c || P->ctx != c) return BCG_ERR_INVALID;
+  CMat G;
+  BCG_TRY(phase_A(c, g, mass, sigma0, T, P, G));
+  return stream_sync(c);
+}
+
 int bcg_context_stream(const bcg_context* c, void** stream_out, int* device_out) {
   if (!c) return BCG_ERR_INVALID;
   if (stream_out) *stream_out = c->stream;

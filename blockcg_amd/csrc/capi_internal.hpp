@@ -193,6 +193,8 @@ int apply_shifted(bcg_context* c, const bcg_gauge* g, double mass, double sigma0
                   int* gram_blocks = nullptr, bool* gram_folded = nullptr, bool* gram_self = nullptr);
 
 // ---- capi_solvers.hip ------------------------------------------------------------------------------
+// Phase A of an iteration: T = (A + sigma0) P ; G = P^dagger T   (:134-140)
+int phase_A(bcg_context* c, const bcg_gauge* g, double mass, double sigma0, bcg_field* T, const bcg_field* P, CMat& G);
 int pair_shifts_depth(const bcg_context* c, int m, int n_shifts);
 int thin_qr(bcg_context* c, bcg_field* y, CMat& R);  // thinQR (inc/fields.hpp:140-146)
 

@@ -1,6 +1,13 @@
 """Parity of the PRODUCTION launch geometry at BASELINE.json's full per-GPU shapes (default tuning: no BCG_HOP_*
 overrides, so 64^4 runs the bundle sweep k_hop4b with 512 blocks over 16x8x8 patches -- k_hop4c for the tile classes --
-exactly what bench.py times).
+the geometry bench.py times).
+
+Which entry point reaches which stencil kernels at 64^4, m = 16 (capi_operator.hip: apply_shifted, factored_pair):
+  D.D (bcg_dirac_hop)            k_hop4b<HOP_PLAIN>
+  D.op (bcg_dirac_apply)         k_hop4b<HOP_PLAIN>, then k_hop4b<HOP_SHIFTED> without a Gram product
+  phase A of SBCGrQ              the factored pair, k_hop4b<HOP_FACT1> and k_hop4b<HOP_FACT2> with its Gram product: the
+                                 launches bench.py times.  Reached only where T and G are wanted together, i.e. through a
+                                 solver iteration or the test aid bcg_debug_phase_a, never through D.D / D.op.
 
 Two independent checks, both against the CPU oracle, neither needs a lattice-sized host computation:
 
@@ -9,13 +16,15 @@ Two independent checks, both against the CPU oracle, neither needs a lattice-siz
     and the device values at those sites are fetched with bcg_field_download_sites.  Sites: every corner of the
     periodic wrap, faces/edges, first and last x3 slice, tile / patch / XCD-class borders, plus uniformly random ones.
     A mis-wrapped slice, a swapped ghost face or a wrong tile offset changes some of these values by O(1).
+    test_operator_production_geometry_vs_sampled_oracle does this for D.D and D.op (the unfactored kernels),
+    test_phase_a_production_geometry_vs_sampled_oracle for the factored pair.
 
  2. Replicated solve.  A base lattice b is tiled r times per direction; the solution of the tiled problem is the
     tiled solution of the base problem, Gram sums scale by prod(r), hence alpha_k, rho_k, beta_s are IDENTICAL, delta_k
     and alpha_s scale by sqrt(prod r), iteration counts agree and X_full(x) = X_base(x mod b).  The oracle solves the base lattice
-    (seconds); the GPU solves the full lattice with every production kernel (fused-Gram stencil, phase B, phase C,
-    reductions over the full grid).  What this cannot see (errors that move data by a multiple of the base extents)
-    is exactly what check 1 sees.
+    (seconds); the GPU solves the full lattice with every production kernel (the factored pair at m = 16 default tuning,
+    the fused-Gram stencil elsewhere, phase B, phase C, reductions over the full grid).  What this cannot see (errors that
+    move data by a multiple of the base extents) is what check 1 sees -- for the factored pair, the second of its tests.
 
 The oracle side of both is validated on the CPU in tests/test_oracle_sampled.py.
 """
@@ -126,6 +135,51 @@ def test_operator_production_geometry_vs_sampled_oracle(bc, orc, case, monkeypat
         got = out.download_sites(sites)
         assert rel_err(got, want) < TOL_KERNEL
         assert np.abs(got - want).max() < 1e-13 * np.abs(want).max()
+    finally:
+        orc.set_threads(1)
+        _release(ctx, psi, out, D)
+
+
+def test_phase_a_production_geometry_vs_sampled_oracle(bc, orc, monkeypatch):
+    """Beside 64c4_m16_default: the same generated U and psi, default tuning, mass 0.37 -- but through one phase A of a solver
+    (the test aid bcg_debug_phase_a, sigma_0 = 0), which takes the factored stencil pair where D.op takes the unfactored
+    kernels.  T at the chosen sites against the oracle's sampled (A psi)(x) by the two assertions above; the Gram matrix as
+    the device summed it, W^dagger W, against hermitian_dot(psi, T) at the bound of the full-size Gram test below.  The one
+    sweep long enough to be paced without forcing (2048 steps per block).  Measured: T 2.2e-16 in the norm, 3.6e-16 per
+    site; G 2.3e-16."""
+    import ctypes
+    dims, m, mass = [64, 64, 64, 64], 16, 0.37
+    for k in ("BCG_HOP_BLOCKS", "BCG_HOP_PATCH", "BCG_HOP_WALK", "BCG_HOP_C2", "BCG_HOP_FACTORED"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv("BCG_FORCE_TILE_CLASSES", "0")
+    ctx = bc.Context(dims)
+    ctx.profiling(True)
+    D = bc.dirac_op(ctx, mass, seed=SEED_U)
+    psi = bc.block_fermion_field(ctx, m).setRandom(seed=SEED_PSI)
+    out = bc.block_fermion_field(ctx, m)
+    sites = chosen_sites(dims)
+    orc.set_threads(8)
+    try:
+        aid, raw = ctx.lib.bcg_debug_phase_a, ctx.lib.bcg_debug_phase_a_gram_raw
+        aid.restype = raw.restype = ctypes.c_int
+        aid.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]
+        raw.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        ctx.check(aid(ctx.h, D.h, mass, 0.0, out.h, psi.h))
+        prof = ctx.profile()
+        assert prof.get("stencil_form_factored_pair", {}).get("count", 0) == 1, sorted(prof)
+        assert prof.get("stencil_form_k_hop4b", {}).get("count", 0) == 2 and "stencil_form_k_hop4c" not in prof, sorted(prof)
+        G = np.zeros((m, m), dtype=np.complex128)  # column-major from the library
+        assert raw(ctx.h, m, G.ctypes.data_as(ctypes.c_void_p)) == 0
+        G = G.T.copy()
+        want = orc.apply_sampled(m, dims, SEED_U, SEED_PSI, mass, sites)
+        got = out.download_sites(sites)
+        e_g = rel_err(G, psi.hermitian_dot(out))
+        print(f"64^4 factored pair: T {rel_err(got, want):.3e} (per site {np.abs(got - want).max() / np.abs(want).max():.3e}), "
+              f"G vs hermitian_dot(psi, T) {e_g:.3e}")
+        assert rel_err(got, want) < TOL_KERNEL
+        assert np.abs(got - want).max() < 1e-13 * np.abs(want).max()  # per site, not only in the norm
+        assert np.array_equal(G, G.conj().T) and np.all(np.diagonal(G).imag == 0.0)
+        assert e_g < 1e-12
     finally:
         orc.set_threads(1)
         _release(ctx, psi, out, D)
