@@ -8,4 +8,5 @@ from ._lib import build, load, LIB_PATH  # noqa: F401
 from .api import (BlockCGError, Context, block_fermion_field, dirac_op, SBCGrQ, SBCGrQState, SUPPORTED_WIDTHS, true_residuals,
                   CG, SCG, BCG, BCGrQ, SBCGrQ_half_volume, SBCGrQ_sum, SBCGrQSumState,
                   gauge_field, fermion_force, NOISE_GAUSSIAN, NOISE_Z2, NOISE_Z4,
-                  shift_sum, covariant_shift, laplacian, smear)  # noqa: F401
+                  shift_sum, covariant_shift, laplacian, smear,
+                  basis_dot, basis_axpy, deflate, low_mode_solution, SBCGrQ_deflated)  # noqa: F401

@@ -206,6 +206,13 @@ class block_fermion_field:
                                                              sites.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), _dp(a)))
         return a
 
+    def copy_columns(self, dst_first, src, src_first, n):
+        """Columns src_first .. src_first + n - 1 of src -> columns dst_first .. of this field; the other columns keep their
+        bits.  The widths may differ (packing and unpacking a wide basis); full or half fields of one parity; src is not
+        this field."""
+        self.ctx.check(self.ctx.lib.bcg_field_copy_columns(self.h, int(dst_first), src.h, int(src_first), int(n)))
+        return self
+
     def copy(self):
         f = block_fermion_field(self.ctx, self.N_rhs)
         self.ctx.check(self.ctx.lib.bcg_field_copy(f.h, self.h))
@@ -500,6 +507,67 @@ def smear(f, links, dir, kappa, n_iter, work=None):
     ctx.check(ctx.lib.bcg_covariant_smear(ctx.h, links.h, f.h, None if work is None else work.h, int(dir), float(kappa),
                                           int(n_iter)))
     return f
+
+
+def _basis_handles(V):
+    V = list(V)
+    if not V:
+        raise ValueError("a basis is a non-empty list of fields")
+    return (ctypes.c_void_p * len(V))(*[v.h for v in V]), len(V), sum(v.N_rhs for v in V)
+
+
+def basis_dot(V, b):
+    """C = V^dagger b as a (K, m) array: V a list of fields of any widths 1..32 (K the sum of the widths, basis column i the
+    column i - offset_k of the field it falls in) of b's context, parity and site count.  Every entry is computed, nothing is
+    mirrored; summed over ranks and identical on every rank (include/blockcg_hip.h, bcg_basis_dot).  b may be one of V."""
+    Vh, nv, K = _basis_handles(V)
+    out = np.empty((b.N_rhs, K), dtype=np.complex128)
+    b.ctx.check(b.ctx.lib.bcg_basis_dot(Vh, nv, b.h, _dp(out)))
+    return np.ascontiguousarray(out.T)
+
+
+def basis_axpy(y, V, C, beta=1.0):
+    """y <- beta y + V C with C a (K, m) array (bcg_basis_axpy).  beta exactly 0 does not read y.  y is none of V."""
+    Vh, nv, K = _basis_handles(V)
+    C = np.asarray(C, dtype=np.complex128)
+    if C.shape != (K, y.N_rhs):
+        raise ValueError(f"expected a {K}x{y.N_rhs} matrix")
+    Ct = np.ascontiguousarray(C.T)  # column-major buffer
+    y.ctx.check(y.ctx.lib.bcg_basis_axpy(y.h, Vh, nv, _dp(Ct), float(beta)))
+    return y
+
+
+def deflate(B, V):
+    """B <- B - V (V^dagger B) for an orthonormal basis V; returns C = V^dagger B, (K, m)."""
+    C = basis_dot(V, B)
+    basis_axpy(B, V, -C, 1.0)
+    return C
+
+
+def low_mode_solution(X, V, evals, C, sigma):
+    """X_s += V (Lambda + sigma_s)^-1 C: the part of (A + sigma_s)^-1 B inside the span of V, for eigenvectors V of A with
+    eigenvalues evals (K of them) and C = V^dagger B.  (A + sigma_s)^-1 is diagonal on eigenvectors of A for every shift at
+    once, so one coefficient matrix per shift is all that changes."""
+    ev = np.asarray(evals, dtype=np.float64)
+    C = np.asarray(C, dtype=np.complex128)
+    if ev.shape != (C.shape[0],) or len(sigma) != len(X):
+        raise ValueError("one eigenvalue per basis column and one shift per X_s are needed")
+    for x, s in zip(X, sigma):
+        basis_axpy(x, V, C / (ev + float(s))[:, None], 1.0)
+    return X
+
+
+def SBCGrQ_deflated(X, B, D, sigma, V, evals, eps=1.e-15, eps_shifts=1.e-15, max_iterations=1000000, return_info=False):
+    """(op + sigma_s) X_s = B with the span of V taken out of the Krylov solve: B is copied, the copy deflated
+    (B - V V^dagger B), SBCGrQ run on it, and the low-mode part V (Lambda + sigma_s)^-1 V^dagger B added to every X_s.
+    Contract: V is orthonormal and evals are its Ritz values of dirac_op::op.  With inexact eigenvectors the result is inexact
+    by their residuals; true_residuals is the check.  Returns the operator applications of the inner solve (or its info)."""
+    Bp = block_fermion_field(B.ctx, B.N_rhs, parity=B.parity)
+    B.ctx.check(B.ctx.lib.bcg_field_copy(Bp.h, B.h))
+    C = deflate(Bp, V)
+    r = SBCGrQ(X, Bp, D, sigma, eps, eps_shifts, max_iterations, consume_B=True, return_info=return_info)
+    low_mode_solution(X, V, evals, C, sigma)
+    return r
 
 
 def _trace_buffers(trace_limit, S, m):

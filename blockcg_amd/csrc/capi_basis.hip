@@ -1,0 +1,206 @@
+// include/blockcg_hip.h: products between fields of unequal width -- C = V^dagger b (bcg_basis_dot) and y <- beta y + V C
+// (bcg_basis_axpy) for a list V of fields whose widths sum to K != m -- and the column copy between widths
+// (bcg_field_copy_columns).  Kernels: kernels_basis.hip.  The host walks V in groups of consecutive fields (one launch per
+// group, kernels_basis.hpp); the K x m matrix lives in c->dev_basis / c->pin_basis, which grow on demand.
+#include "capi_internal.hpp"
+#include "kernels_basis.hpp"
+
+namespace bcg_impl {
+namespace {
+
+struct BasisGroup {
+  bool mfma;
+  int first, count;  // fields V[first .. first + count - 1]
+  int K, off;        // its columns off .. off + K - 1 of the basis
+};
+
+// V[0 .. nv-1] against a field `like`: one context, parity and site count; returns K, or -1
+int64_t basis_columns(const bcg_field* const* V, int nv, const bcg_field* like) {
+  if (!V || nv < 1 || !like) return -1;
+  int64_t K = 0;
+  for (int k = 0; k < nv; ++k) {
+    const bcg_field* v = V[k];
+    if (!v || v->ctx != like->ctx || v->parity != like->parity || v->sites != like->sites) return -1;
+    K += v->m;
+  }
+  return K;
+}
+
+// Consecutive fields of one class (MFMA: m and the width in {16, 32}) up to the form's bound (mfma_blocks blocks of 16
+// columns in the MFMA form); max_cols: a further bound on the columns of a group (the dot's block partials must fit
+// c->partials: the group shrinks, not the grid)
+std::vector<BasisGroup> basis_groups(const bcg_context* c, const bcg_field* const* V, int nv, int m, int mfma_blocks, int max_cols) {
+  std::vector<BasisGroup> out;
+  const bool fast = !c->force_generic && (m == 16 || m == 32);
+  int off = 0;
+  for (int k = 0; k < nv;) {
+    BasisGroup g{fast && bcg::basis_mfma_width(V[k]->m), k, 0, 0, off};
+    const int cols = std::min(max_cols, g.mfma ? 16 * mfma_blocks : bcg::kBasisGenericCols);
+    const int fields = g.mfma ? mfma_blocks : bcg::kBasisGenericFields;
+    while (k < nv && g.count < fields && (fast && bcg::basis_mfma_width(V[k]->m)) == g.mfma &&
+           (g.count == 0 || g.K + V[k]->m <= cols)) {
+      g.K += V[k]->m;
+      g.count += 1;
+      k += 1;
+    }
+    off += g.K;
+    out.push_back(g);
+  }
+  return out;
+}
+
+bcg::BasisBlocks group_blocks(const bcg_field* const* V, const BasisGroup& g, int* nblocks16) {
+  bcg::BasisBlocks b{};
+  int n = 0;
+  for (int k = g.first; k < g.first + g.count; ++k)
+    for (int c0 = 0; c0 < V[k]->m; c0 += 16) {
+      b.p[n] = V[k]->d + c0;
+      b.ld[n] = V[k]->m;
+      n += 1;
+    }
+  *nblocks16 = n;
+  return b;
+}
+
+bcg::BasisFields group_fields(const bcg_field* const* V, const BasisGroup& g) {
+  bcg::BasisFields f{};
+  f.nv = g.count;
+  f.K = g.K;
+  int off = 0;
+  for (int k = 0; k < g.count; ++k) {
+    f.v[k] = V[g.first + k]->d;
+    f.w[k] = V[g.first + k]->m;
+    f.off[k] = off;
+    off += f.w[k];
+  }
+  return f;
+}
+
+void release_basis(bcg_context* c) {
+  if (c->dev_basis) (void)hipFree(c->dev_basis);
+  if (c->pin_basis) (void)hipHostFree(c->pin_basis);
+  c->dev_basis = nullptr;
+  c->pin_basis = nullptr;
+  c->basis_entries = 0;
+}
+
+int ensure_basis(bcg_context* c, size_t entries) {
+  if (!c->basis_uploaded) HIP_TRY(c, hipEventCreateWithFlags(&c->basis_uploaded, hipEventDisableTiming));
+  if (entries <= c->basis_entries) return BCG_OK;
+  BCG_TRY(stream_sync(c));  // a kernel of an earlier call may still read the old buffer
+  release_basis(c);
+  HIP_TRY(c, hipMalloc(&c->dev_basis, entries * sizeof(double2)));
+  HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&c->pin_basis), entries * sizeof(double2), hipHostMallocDefault));
+  c->basis_entries = entries;
+  return BCG_OK;
+}
+
+}  // namespace
+}  // namespace bcg_impl
+
+using namespace bcg_impl;
+
+extern "C" {
+
+int bcg_basis_dot(const bcg_field* const* V, int nv, const bcg_field* b, double* out) {
+  DeviceScope on_device(b ? b->ctx : nullptr);
+  const int64_t K = basis_columns(V, nv, b);
+  if (K < 0 || !out) return BCG_ERR_INVALID;
+  bcg_context* c = b->ctx;
+  if (c->distributed && (!c->have_comm || !c->comm.allreduce_sum))
+    BCG_FAIL(c, BCG_ERR_COMM, "lattice is split over ranks but no bcg_comm was set");
+  const int m = b->m;
+  const size_t entries = static_cast<size_t>(K) * m;
+  if (entries > (static_cast<size_t>(1) << 30)) BCG_FAIL(c, BCG_ERR_UNSUPPORTED, "bcg_basis_dot: more than 2^30 entries");
+  int rc = ensure_scratch(c);
+  if (rc == BCG_OK) rc = ensure_basis(c, entries);
+  rc = agree_on_allocation(c, rc, "bcg_basis_dot", "the K x m result");
+  if (rc != BCG_OK) {
+    if (c->distributed) release_basis(c);  // every rank starts the next call from the same state
+    return rc;
+  }
+  const int64_t room = static_cast<int64_t>(c->partials_bytes / sizeof(double2)) / (static_cast<int64_t>(bcg::kBasisBlocks) * m);
+  if (room < 32) BCG_FAIL(c, BCG_ERR_UNSUPPORTED, "bcg_basis_dot: the block partials do not fit the context's scratch");
+  for (const BasisGroup& g : basis_groups(c, V, nv, m, bcg::basis_dot_mfma_blocks(m), static_cast<int>(std::min<int64_t>(room, 1 << 20)))) {
+    int nblocks;
+    {
+      ProfScope ps(c, "basis_dot", static_cast<double>(b->sites) * 48.0 * (g.K + m), static_cast<double>(rows_of(b)) * 8.0 * g.K * m);
+      ProfScope form(c, g.mfma ? "basis_form_mfma" : "basis_form_generic");
+      if (g.mfma) {
+        int n16;
+        const bcg::BasisBlocks blocks = group_blocks(V, g, &n16);
+        nblocks = bcg::launch_basis_dot_mfma(c->stream, m, n16, rows_of(b), blocks, b->d, c->partials);
+      } else {
+        nblocks = bcg::launch_basis_dot_generic(c->stream, m, rows_of(b), group_fields(V, g), b->d, c->partials);
+      }
+    }
+    BCG_TRY(check_launch(c, "basis_dot"));
+    {
+      ProfScope ps(c, "basis_fold");
+      bcg::launch_basis_fold(c->stream, g.K, m, nblocks, c->partials, c->dev_basis, static_cast<int>(K), g.off);
+    }
+    BCG_TRY(check_launch(c, "basis_fold"));
+  }
+  if (c->distributed) {
+    ProfScope ps(c, "allreduce");
+    if (c->comm.allreduce_sum(c->comm.user, c->dev_basis, 2 * entries) != 0) BCG_FAIL(c, BCG_ERR_COMM, "allreduce_sum callback failed");
+  }
+  HIP_TRY(c, hipEventSynchronize(c->basis_uploaded));  // an upload of bcg_basis_axpy may still read pin_basis
+  HIP_TRY(c, hipMemcpyAsync(c->pin_basis, c->dev_basis, entries * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
+  BCG_TRY(stream_sync(c));
+  std::memcpy(out, c->pin_basis, entries * sizeof(double2));
+  return BCG_OK;
+}
+
+int bcg_basis_axpy(bcg_field* y, const bcg_field* const* V, int nv, const double* C, double beta) {
+  DeviceScope on_device(y ? y->ctx : nullptr);
+  const int64_t K = basis_columns(V, nv, y);
+  if (K < 0 || !C) return BCG_ERR_INVALID;
+  bcg_context* c = y->ctx;
+  for (int k = 0; k < nv; ++k)
+    if (V[k] == y) BCG_FAIL(c, BCG_ERR_INVALID, "bcg_basis_axpy: y is one of the basis fields");
+  if (!std::isfinite(beta)) BCG_FAIL(c, BCG_ERR_INVALID, "bcg_basis_axpy: beta is not finite");
+  const int m = y->m;
+  const size_t entries = static_cast<size_t>(K) * m;
+  if (entries > (static_cast<size_t>(1) << 30)) BCG_FAIL(c, BCG_ERR_UNSUPPORTED, "bcg_basis_axpy: more than 2^30 entries");
+  BCG_TRY(ensure_basis(c, entries));
+  HIP_TRY(c, hipEventSynchronize(c->basis_uploaded));  // the previous upload has left pin_basis
+  std::memcpy(c->pin_basis, C, entries * sizeof(double2));
+  HIP_TRY(c, hipMemcpyAsync(c->dev_basis, c->pin_basis, entries * sizeof(double2), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipEventRecord(c->basis_uploaded, c->stream));
+  bool first = true;
+  for (const BasisGroup& g : basis_groups(c, V, nv, m, bcg::basis_axpy_mfma_blocks(m), 1 << 20)) {
+    const double bg = first ? beta : 1.0;
+    {
+      ProfScope ps(c, "basis_axpy", static_cast<double>(y->sites) * 48.0 * (g.K + (bg == 0.0 ? m : 2 * m)),
+                   static_cast<double>(rows_of(y)) * 8.0 * g.K * m);
+      ProfScope form(c, g.mfma ? "basis_form_mfma" : "basis_form_generic");
+      if (g.mfma) {
+        int n16;
+        const bcg::BasisBlocks blocks = group_blocks(V, g, &n16);
+        bcg::launch_basis_axpy_mfma(c->stream, m, n16, rows_of(y), y->d, blocks, c->dev_basis, static_cast<int>(K), g.off, bg);
+      } else {
+        bcg::launch_basis_axpy_generic(c->stream, m, rows_of(y), y->d, group_fields(V, g), c->dev_basis, static_cast<int>(K), g.off, bg);
+      }
+    }
+    BCG_TRY(check_launch(c, "basis_axpy"));
+    first = false;
+  }
+  return BCG_OK;
+}
+
+int bcg_field_copy_columns(bcg_field* dst, int dst_first, const bcg_field* src, int src_first, int n) {
+  DeviceScope on_device(dst ? dst->ctx : nullptr);
+  if (!dst || !src || dst == src || dst->ctx != src->ctx || dst->parity != src->parity || dst->sites != src->sites)
+    return BCG_ERR_INVALID;
+  bcg_context* c = dst->ctx;
+  if (n < 1 || dst_first < 0 || src_first < 0 || dst_first > dst->m - n || src_first > src->m - n)
+    BCG_FAIL(c, BCG_ERR_INVALID, "bcg_field_copy_columns: column range outside a field");
+  {
+    ProfScope ps(c, "copy_columns", static_cast<double>(dst->sites) * 48.0 * 2 * n);
+    bcg::launch_copy_columns(c->stream, rows_of(dst), dst->d, dst->m, dst_first, src->d, src->m, src_first, n);
+  }
+  return check_launch(c, "copy_columns");
+}
+
+}  // extern "C"

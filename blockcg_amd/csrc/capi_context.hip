@@ -449,6 +449,9 @@ int bcg_context_destroy(bcg_context* c) {
   if (c->dev_gram) (void)hipFree(c->dev_gram);
   if (c->fold_tickets) (void)hipFree(c->fold_tickets);
   if (c->pin_gram) (void)hipHostFree(c->pin_gram);
+  if (c->dev_basis) (void)hipFree(c->dev_basis);
+  if (c->pin_basis) (void)hipHostFree(c->pin_basis);
+  if (c->basis_uploaded) (void)hipEventDestroy(c->basis_uploaded);
   if (c->staging) (void)hipFree(c->staging);
   for (int k = 0; k < 2; ++k) {  // the upload / download pipeline (ensure_xfer)
     if (c->xfer_stream[k]) (void)hipStreamSynchronize(c->xfer_stream[k]);

@@ -5,6 +5,7 @@
 //   capi_force.hip      the fermion force of multi-shift solutions (bcg_force_accumulate), gauge-field download / zero
 //   capi_sources.hip    noise fields, point / wall sources, the slice-resolved inner product
 //   capi_shift.hip      the covariant nearest-neighbour sum with free coefficients, covariant smearing
+//   capi_basis.hip      products between fields of unequal width (V^dagger b, y <- beta y + V C), the column copy
 // Host code only; every loop over lattice sites is a HIP kernel (kernels_generic.hip, kernels_mfma.hip, kernels_stencil.hip).
 #pragma once
 #include <hip/hip_runtime.h>

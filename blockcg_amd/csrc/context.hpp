@@ -92,6 +92,10 @@ struct bcg_context {
   unsigned* fold_tickets = nullptr;      // 9 words: arrival counters of the in-kernel Gram fold (bcg::GramFold)
   double2* dev_gram = nullptr;           // reduced Gram matrix (device), all-reduced in place
   double* pin_gram = nullptr;            // pinned host copy
+  double2* dev_basis = nullptr;          // K x m matrix of bcg_basis_dot (all-reduced in place) / bcg_basis_axpy (capi_basis.hip)
+  double* pin_basis = nullptr;           // pinned host copy
+  size_t basis_entries = 0;              // complex entries either holds; grown on demand
+  hipEvent_t basis_uploaded = nullptr;   // the last upload from pin_basis has left the host buffer
   double2* staging = nullptr;            // layout-conversion staging of bcg_field_download_sites
   size_t staging_bytes = 0;
   // host <-> device pipeline of bcg_field_upload / bcg_field_download: two chunks in flight, each with its own stream,

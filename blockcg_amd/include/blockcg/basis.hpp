@@ -1,0 +1,124 @@
+// blockcg/basis.hpp -- products between a solve block and a basis of another width, and deflation on top of them
+// (include/blockcg_hip.h: bcg_basis_dot, bcg_basis_axpy, bcg_field_copy_columns).
+//
+//   basis V;  V.push_back(f)                     a list of fields of any widths 1 .. 32; K = the sum of the widths
+//   basis_dot(V, b)                              C = V^dagger b, K x m column-major (element (i, j) at j * K + i)
+//   basis_axpy(y, V, C, beta = 1)                y <- beta y + V C; beta == 0 does not read y
+//   copy_columns(dst, dst_first, src, src_first, n)   n columns between fields of different widths
+//   deflate(B, V)                                B <- B - V (V^dagger B); returns C = V^dagger B
+//   low_mode_solution(X, V, evals, C, sigma)     X_s += V (Lambda + sigma_s)^-1 C
+//   SBCGrQ_deflated(X, B, D, sigma, V, evals, ...)    copies B, deflates the copy, runs SBCGrQ, adds the low-mode part
+//
+// Contract of the last three: V is orthonormal and evals are its Ritz values of dirac_op::op.  (A + sigma_s)^-1 is
+// diagonal on eigenvectors of A for every shift at once, which is what makes deflating a multi-shift solve cheap.  With
+// inexact eigenvectors the result is inexact by their residuals; the reference's true-residual measure is the check.
+// The reference has none of these; they are extensions in the blockcg namespace, host compiler only like the other headers.
+#ifndef BLOCKCG_BASIS_HPP
+#define BLOCKCG_BASIS_HPP
+#include <complex>
+#include <functional>
+#include <stdexcept>
+#include <vector>
+
+#include "block_solvers.hpp"
+#include "dirac_op.hpp"
+#include "fields.hpp"
+
+namespace blockcg {
+
+// A list of fields of one lattice, parity and site count.  The fields are referred to, not copied: they outlive the basis.
+class basis {
+ public:
+  template <int W>
+  void push_back(const block_fermion_field<W>& f) {
+    static_assert(W >= 1 && W <= 32, "a basis field has 1 .. 32 columns");
+    const block_fermion_field<W>* p = &f;
+    h_.push_back(f.handle());
+    flush_.push_back([p] { p->flush(); });
+    K_ += W;
+    lat_ = &f.lat();
+  }
+  int K() const { return K_; }
+  int size() const { return static_cast<int>(h_.size()); }
+  const bcg_field* const* handles() const { return h_.data(); }
+  lattice& lat() const {
+    if (!lat_) throw std::invalid_argument("basis: empty");
+    return *lat_;
+  }
+  void flush() const {
+    for (const auto& f : flush_) f();
+  }
+
+ private:
+  std::vector<const bcg_field*> h_;
+  std::vector<std::function<void()>> flush_;
+  int K_ = 0;
+  lattice* lat_ = nullptr;
+};
+
+typedef std::vector<std::complex<double>> basis_matrix;  // K x m, column-major
+
+template <int N_rhs>
+basis_matrix basis_dot(const basis& V, const block_fermion_field<N_rhs>& b) {
+  V.flush();
+  b.flush();
+  basis_matrix C(static_cast<size_t>(V.K()) * N_rhs);
+  check(bcg_basis_dot(V.handles(), V.size(), b.handle(), reinterpret_cast<double*>(C.data())), V.lat().ctx(), "basis_dot");
+  return C;
+}
+
+template <int N_rhs>
+void basis_axpy(block_fermion_field<N_rhs>& y, const basis& V, const basis_matrix& C, double beta = 1.0) {
+  if (C.size() != static_cast<size_t>(V.K()) * N_rhs) throw std::invalid_argument("basis_axpy: C is K x m");
+  V.flush();
+  y.flush();
+  check(bcg_basis_axpy(y.handle(), V.handles(), V.size(), reinterpret_cast<const double*>(C.data()), beta), V.lat().ctx(),
+        "basis_axpy");
+  y.device_written();
+}
+
+template <int N_dst, int N_src>
+void copy_columns(block_fermion_field<N_dst>& dst, int dst_first, const block_fermion_field<N_src>& src, int src_first, int n) {
+  src.flush();
+  dst.flush();
+  check(bcg_field_copy_columns(dst.handle(), dst_first, src.handle(), src_first, n), src.lat().ctx(), "copy_columns");
+  dst.device_written();
+}
+
+template <int N_rhs>
+basis_matrix deflate(block_fermion_field<N_rhs>& B, const basis& V) {
+  basis_matrix C = basis_dot(V, B), minus(C.size());
+  for (size_t e = 0; e < C.size(); ++e) minus[e] = -C[e];
+  basis_axpy(B, V, minus, 1.0);
+  return C;
+}
+
+template <int N_rhs>
+void low_mode_solution(std::vector<block_fermion_field<N_rhs>>& X, const basis& V, const std::vector<double>& evals,
+                       const basis_matrix& C, const std::vector<double>& sigma) {
+  const size_t K = static_cast<size_t>(V.K());
+  if (evals.size() != K || C.size() != K * N_rhs || sigma.size() != X.size())
+    throw std::invalid_argument("low_mode_solution: one eigenvalue per basis column, C of size K x m, one shift per X_s");
+  basis_matrix W(C.size());
+  for (size_t s = 0; s < X.size(); ++s) {
+    for (size_t j = 0; j < static_cast<size_t>(N_rhs); ++j)
+      for (size_t i = 0; i < K; ++i) W[j * K + i] = C[j * K + i] / (evals[i] + sigma[s]);
+    basis_axpy(X[s], V, W, 1.0);
+  }
+}
+
+// Returns the operator applications of the inner solve.
+template <int N_rhs>
+int SBCGrQ_deflated(std::vector<block_fermion_field<N_rhs>>& X, const block_fermion_field<N_rhs>& B, const dirac_op& D,
+                    std::vector<double>& sigma, const basis& V, const std::vector<double>& evals, double eps = 1.e-15,
+                    double eps_shifts = 1.e-15, int max_iterations = 1e6) {
+  block_fermion_field<N_rhs> Bp(B);
+  const basis_matrix C = deflate(Bp, V);
+  const int iterations = SBCGrQ_consuming_source(X, Bp, D, sigma, eps, eps_shifts, max_iterations);
+  low_mode_solution(X, V, evals, C, sigma);
+  return iterations;
+}
+
+}  // namespace blockcg
+
+#endif

@@ -400,6 +400,34 @@ int bcg_dirac_shift_sum(bcg_context* ctx, const bcg_gauge* g, bcg_field* out, co
 int bcg_covariant_smear(bcg_context* ctx, const bcg_gauge* g, bcg_field* f, bcg_field* work, int dir, double kappa,
                         int n_iter);
 
+/* ---- products with a basis of another width (extensions) ----------------------------------------
+ * V is a list of nv >= 1 fields of one context, of any widths 1 .. 32, with the parity and site count of b / y.  K is the
+ * sum of the widths; basis column i is column i - offset_k of the field it falls in.  K x m matrices cross the ABI
+ * column-major, interleaved (re, im), as everywhere else.  The host walks V in groups of consecutive fields, one launch per
+ * group, so that b is read once (y read and written once) per group and not per field.  m in {16, 32} and widths in
+ * {16, 32} take the MFMA form (up to 64 basis columns per launch at m = 16; 32 for the dot and 48 for the update at m = 32),
+ * every other combination and bcg_force_generic the generic form (up to 32 columns per launch); one call may use both.  No
+ * atomics: the same bits on every call.
+ *  - Profile keys "basis_dot" (48 (K_g + m) bytes per site and group) and "basis_axpy" (48 (K_g + 2 m), or 48 (K_g + m)
+ *    for a first group with beta == 0), 8 K_g m flops per row; "basis_form_mfma" / "basis_form_generic" count the launches
+ *    of either form.
+ *  - The K x m result and the uploaded coefficients live in a buffer of the context's own (device and pinned host, 16 K m
+ *    bytes each), allocated on first use, grown when a larger K m arrives, freed by bcg_context_destroy.
+ *
+ * bcg_basis_dot: out[j*K + i] = sum_{x,c} conj(V_i(x,c)) b_j(x,c); every entry is computed, nothing is mirrored.  Block
+ * partials are summed in ascending block order, then over ranks with ONE bcg_comm.allreduce_sum of the whole matrix:
+ * identical on every rank.  b may be one of the V_k.  Synchronizes the stream.
+ * bcg_basis_axpy: y <- beta y + sum_i V_i C(i, .), C of size K x m.  beta exactly 0 does not read y (a NaN there does not
+ * survive).  y must not be one of the V_k.
+ * bcg_field_copy_columns: columns src_first .. src_first + n - 1 of src go to columns dst_first .. of dst; the other
+ * columns of dst keep their bits.  The widths may differ; full or half fields of one parity; dst != src.
+ * BCG_ERR_INVALID: a NULL pointer, nv < 1, mixed contexts, parities or site counts, y among the V_k, dst == src, n < 1 or a
+ * column range outside a field, a non-finite beta.  BCG_ERR_COMM (bcg_basis_dot): a divided lattice without a bcg_comm.
+ * The arguments are checked before the first launch: a call that fails them leaves out / y / dst exactly as they were. */
+int bcg_basis_dot(const bcg_field* const* V, int nv, const bcg_field* b, double* out);
+int bcg_basis_axpy(bcg_field* y, const bcg_field* const* V, int nv, const double* C, double beta);
+int bcg_field_copy_columns(bcg_field* dst, int dst_first, const bcg_field* src, int src_first, int n);
+
 #ifdef __cplusplus
 }
 #endif
