@@ -4,14 +4,18 @@ against their numpy restatement (tests/basis_ref.py), and the deflated solve com
 Tolerances: EPS_DOT = 1e-13 per entry of the dot relative to sqrt(|V_i|^2 |b_j|^2) (the bound of tests/test_slice_gram.py
 for sums of this length and shorter ones), TOL_KERNEL for the update, TOL_SOLUTION for the solutions of the deflated solve.
 Shapes: rows that are no multiple of 16 and 3-row sites ([5,3,2], [37]), both half parities ([4,2,4,2]), every width class
-of either form, both forms in one call, more than one group per call and more than one block per launch."""
+of either form, both forms in one call, more than one group per call and more than one block per launch; the host's group
+walk with the launch counts of the dot and of the update asserted separately (GROUP_WALK); blockcg/basis.hpp run on the device
+(tests/cpp/basis_run_probe.cpp)."""
 import ctypes
+import os
+import subprocess
 
 import numpy as np
 import pytest
 
 import basis_ref as ref
-from conftest import TOL_KERNEL, TOL_SOLUTION, rel_err
+from conftest import ROOT, TOL_KERNEL, TOL_SOLUTION, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -22,6 +26,23 @@ LATTICES = ([5, 3, 2], [37], [4, 2, 4, 2])
 GENERIC = (([5], 1, 0, 1), ([1, 7, 12], 5, 0, 1), ([8, 8], 8, 0, 1), ([32, 3], 12, 0, 2))
 MFMA = (([16], 16, 1, 0), ([32], 16, 1, 0), ([16], 32, 1, 0), ([32], 32, 1, 0), ([16, 32, 16], 16, 1, 0))
 MIXED = (([16, 5], 16, 1, 1),)
+# The group walk (capi_basis.hip: basis_groups): (widths of V, m, (MFMA, generic) launches of the dot, the same of the update).
+# The counts follow from the bounds of kernels_basis.hpp: a generic group holds at most 32 columns and 8 fields; an MFMA group
+# at most 4 blocks of 16 columns at m = 16, and at m = 32 2 blocks for the dot and 3 for the update, never more fields than
+# blocks; a group ends where the form changes.  The first three rows are the only launches of the update on three blocks at
+# m = 32, the first five the only ones of the m = 32 dot (and of its fold) on a second group.
+GROUP_WALK = (
+    ([16, 16, 16], 32, (2, 0), (1, 0)),        # dot 16 16 | 16; update 16 16 16
+    ([32, 16], 32, (2, 0), (1, 0)),            # dot 32 | 16; update 32 16
+    ([16, 32], 32, (2, 0), (1, 0)),            # dot 16 | 32; update 16 32
+    ([32, 32, 16, 16], 32, (3, 0), (3, 0)),    # dot 32 | 32 | 16 16; update 32 | 32 16 | 16
+    ([16, 7, 32], 32, (2, 1), (2, 1)),         # 16 | 7 | 32: the forms alternate
+    ([16] * 5, 16, (2, 0), (2, 0)),            # 16 16 16 16 | 16
+    ([16, 5, 32, 3, 16], 16, (3, 2), (3, 2)),  # the forms alternate four times
+    ([1] * 9, 3, (0, 2), (0, 2)),              # the generic bound of 8 fields, 8 columns in all
+    ([4] * 9, 12, (0, 2), (0, 2)),             # 8 fields and 32 columns at once
+    ([12, 12, 12], 5, (0, 2), (0, 2)),         # 12 12 | 12: the column bound before the field bound
+)
 
 
 @pytest.fixture(scope="module")
@@ -72,7 +93,8 @@ def _dot_error(got, want, scale):
     return float(np.max(np.abs(got - want) / scale))
 
 
-def _case(bc, ctx, widths, m, parity, n_mfma, n_generic, worst):
+def _case(bc, ctx, widths, m, parity, dot_forms, axpy_forms, worst):
+    """dot_forms, axpy_forms: the expected (MFMA, generic) launch counts of basis_dot and of basis_axpy"""
     what = (ctx.dims, widths, m, parity)
     V, b, y = _operands(bc, ctx, widths, m, parity)
     Vh, bh, yh = [v.download() for v in V], b.download(), y.download()
@@ -81,12 +103,14 @@ def _case(bc, ctx, widths, m, parity, n_mfma, n_generic, worst):
     rng = np.random.default_rng(K * 100 + m)
     C = rng.standard_normal((K, m)) + 1j * rng.standard_normal((K, m))
     results = {}
-    forms = {False: (n_mfma, n_generic), True: (0, _generic_launches(widths))}
+    generic_forms = (0, _generic_launches(widths))
+    dot_expected = {False: tuple(dot_forms), True: generic_forms}
+    axpy_expected = {False: tuple(axpy_forms), True: generic_forms}
     for generic in (False, True):
         ctx.force_generic(generic)
         ctx.profile_reset()
         got = bc.basis_dot(V, b)
-        assert _forms(ctx) == forms[generic], what
+        assert _forms(ctx) == dot_expected[generic], (what, "dot")
         err = _dot_error(got, want, scale)
         worst[0] = max(worst[0], err)
         assert err <= EPS_DOT, (what, generic, err)
@@ -96,7 +120,7 @@ def _case(bc, ctx, widths, m, parity, n_mfma, n_generic, worst):
             y.upload(np.full_like(yh, np.nan) if beta == 0.0 else yh)
             ctx.profile_reset()
             bc.basis_axpy(y, V, C, beta)
-            assert _forms(ctx) == forms[generic], what
+            assert _forms(ctx) == axpy_expected[generic], (what, "update")
             out = y.download()
             assert np.isfinite(out).all(), (what, beta)
             e = rel_err(out, ref.basis_axpy(yh, Vh, C, beta))
@@ -121,17 +145,31 @@ def _case(bc, ctx, widths, m, parity, n_mfma, n_generic, worst):
 @pytest.mark.parametrize("widths,m,n_mfma,n_generic", GENERIC + MFMA + MIXED)
 def test_basis_products(bc, widths, m, n_mfma, n_generic):
     worst = [0.0, 0.0]
+    forms = (n_mfma, n_generic)
     for dims in LATTICES:
-        _case(bc, _ctx(bc, dims), widths, m, None, n_mfma, n_generic, worst)
+        _case(bc, _ctx(bc, dims), widths, m, None, forms, forms, worst)
     for parity in (0, 1):
-        _case(bc, _ctx(bc, [4, 2, 4, 2]), widths, m, parity, n_mfma, n_generic, worst)
+        _case(bc, _ctx(bc, [4, 2, 4, 2]), widths, m, parity, forms, forms, worst)
     print(f"V widths {widths}, m = {m}: dot {worst[0]:.3e} of |V_i||b_j|, update {worst[1]:.3e} relative")
+
+
+@pytest.mark.parametrize("widths,m,dot_forms,axpy_forms", GROUP_WALK)
+def test_group_walk(bc, widths, m, dot_forms, axpy_forms):
+    """The host's walk over groups of basis fields, where the dot and the update may cut V differently: the launch counts of
+    either call from the profile, and everything test_basis_products checks, on the same lattices and parities."""
+    worst = [0.0, 0.0]
+    for dims in LATTICES:
+        _case(bc, _ctx(bc, dims), widths, m, None, dot_forms, axpy_forms, worst)
+    for parity in (0, 1):
+        _case(bc, _ctx(bc, [4, 2, 4, 2]), widths, m, parity, dot_forms, axpy_forms, worst)
+    print(f"V widths {widths}, m = {m}: dot {worst[0]:.3e} of |V_i||b_j|, update {worst[1]:.3e} relative; "
+          f"launches dot {dot_forms}, update {axpy_forms}")
 
 
 def test_more_than_one_group(bc):
     """Five fields of 32 columns at m = 16: three launches of the MFMA form (64, 64 and 32 columns)."""
     worst = [0.0, 0.0]
-    _case(bc, _ctx(bc, [4, 2, 4, 2]), [32] * 5, 16, None, 3, 0, worst)
+    _case(bc, _ctx(bc, [4, 2, 4, 2]), [32] * 5, 16, None, (3, 0), (3, 0), worst)
     print(f"five fields of 32, m = 16: dot {worst[0]:.3e}, update {worst[1]:.3e}")
 
 
@@ -299,3 +337,34 @@ def test_sbcgrq_deflated(bc):
         assert errs[s][0] <= TOL_SOLUTION, (s, errs[s])
         assert res_deflated[s].max() <= 10.0 * res_plain[s].max(), (s, res_deflated[s].max(), res_plain[s].max())
     assert it_deflated <= 0.85 * it_plain, (it_deflated, it_plain)
+
+
+def test_cpp_basis_layer_runs(bc):
+    """tests/cpp/basis_run_probe.cpp, built by the recipe of tests/test_cpp_dropin.py: blockcg/basis.hpp on the device -- the
+    column-major C[j * K + i], the host mirror around every call, copy_columns, deflate -- checked inside the probe against
+    host sums in long double; and its SBCGrQ_deflated (V = 16 orthonormal columns, evals 1 .. 16: no solution of the system,
+    but a fixed function of its inputs) against the same calls made here."""
+    from test_cpp_dropin import _compile
+    exe = _compile(os.path.join(ROOT, "tests", "cpp", "basis_run_probe.cpp"), "basis_run_probe")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    print(r.stdout)
+    lines = r.stdout.splitlines()
+    assert r.returncode == 0 and lines and lines[-1] == "BASIS_PROBE_OK" and "FAILED" not in r.stdout, r.stdout + r.stderr
+    applications = [int(line.split()[1]) for line in lines if line.startswith("DEFLATED_APPLICATIONS")]
+    hdot = {int(line.split()[1]): np.array([float(v) for v in line.split()[2:]]) for line in lines if line.startswith("HDOT")}
+    sigma = [0.0, 0.05, 0.5]
+    assert len(applications) == 1 and sorted(hdot) == [0, 1, 2]
+    ctx = _ctx(bc, [4, 2, 4, 2])
+    q = bc.block_fermion_field(ctx, 16).setGaussian(31)
+    q.thinQR()
+    D = bc.dirac_op(ctx, 0.5, seed=7)
+    B = bc.block_fermion_field(ctx, 8).setGaussian(32)
+    X = [bc.block_fermion_field(ctx, 8) for _ in sigma]
+    assert bc.SBCGrQ_deflated(X, B, D, sigma, [q], np.arange(1.0, 17.0), 1e-10, 1e-10) == applications[0]
+    for s in range(len(sigma)):
+        assert hdot[s].shape == (128,)
+        got = (hdot[s][0::2] + 1j * hdot[s][1::2]).reshape(8, 8).T  # the probe prints column-major
+        want = B.hermitian_dot(X[s])
+        err = np.linalg.norm(got - want) / np.linalg.norm(want)
+        print(f"sigma = {sigma[s]}: B^dagger X_s of the C++ layer against the bindings {err:.3e}")
+        assert err <= TOL_SOLUTION, (s, err)

@@ -121,7 +121,7 @@ def _report(line):
         pass
 
 
-@pytest.mark.parametrize("m", [5, 7, 9, 10, 11, 13, 14, 15, 17, 19, 20, 23, 24, 27, 29, 31])
+@pytest.mark.parametrize("m", [5, 7, 9, 10, 11, 13, 14, 15, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31])
 def test_every_block_width(bc, orc, m):
     """The reference's N_rhs is an arbitrary template int (inc/fields.hpp:19-26): every 1 <= m <= 32 exists here (generic
     kernels outside 8, 16, 32).  Per width: every field primitive and the operator against the oracle (pinned to the

@@ -1,7 +1,8 @@
 """Half-volume (parity-decoupled) solve, SURVEY.md section 8f-4 / Appendix D: dirac_op::D couples opposite site parities only
 (inc/dirac_op.hpp:14-21), so op = mass^2 - D^2 (inc/dirac_op.hpp:36-43) is block diagonal in the parity and the multi-shift
 solve splits into two solves on V/2 sites.  Checked against the full-volume oracle: the parity-compact layout, the
-operator blocks, every field primitive on half fields, and the solve itself."""
+operator blocks, two field primitives on half fields (hermitian_dot of a field with itself, add with a matrix), and the solve
+itself.  Every field primitive on half fields, at every block width: tests/test_every_width.py."""
 import numpy as np
 import pytest
 
