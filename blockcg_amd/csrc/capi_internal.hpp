@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "context.hpp"
+#include "hop_plan.hpp"
 #include "kernels_mfma.hpp"
 
 #define BCG_FAIL(ctx, code, msg) \
@@ -71,7 +72,6 @@ struct ProfScope {
   bcg_context* c;
   bcg::ProfEntry* e = nullptr;
   hipEvent_t a = nullptr, b = nullptr;
-  double booked_bytes = 0.0, booked_flops = 0.0;
   // alg_bytes: the ALGORITHMIC HBM bytes of what is launched inside the scope (per-site figure x the
   // sites this launch processes); summed per kernel class so that bench.py's roofline is right for split launches
   // (phase C in two launches, capacity-mode windows) too.
@@ -82,20 +82,9 @@ struct ProfScope {
     e = &c->prof[name];
     e->bytes += alg_bytes;
     e->flops += alg_flops;
-    booked_bytes = alg_bytes;
-    booked_flops = alg_flops;
     a = take();
     b = take();
     (void)hipEventRecord(a, c->stream);
-  }
-  // nothing was launched inside the scope after all (a launcher declined): book nothing, count nothing
-  void cancel() {
-    if (!e) return;
-    e->bytes -= booked_bytes;
-    e->flops -= booked_flops;
-    c->event_pool.push_back(a);
-    c->event_pool.push_back(b);
-    e = nullptr;
   }
   ~ProfScope() {
     if (!e) return;
@@ -177,6 +166,8 @@ inline bool can_overlap(const bcg_context* c) {
   return c->distributed && c->have_comm && c->comm.halo_exchange_begin && c->comm.halo_exchange_end;
 }
 int halo_field(bcg_context* c, const bcg_field* f, bool split = false);
+// the plan of one stencil launch on this context (after ensure_scratch); HOP_FORM_NONE: no specialised kernel serves it
+bcg::HopLaunchPlan plan_stencil(const bcg_context* c, const bcg::LatticeDev& lat, bcg::HopTuning tune, const bcg::HopRequest& rq);
 int halo_gauge(bcg_context* c, bcg_gauge* g);  // the gauge ghost (minus faces of U_mu), once per upload
 // out = D in (HOP_PLAIN) or c0 * p - D in (HOP_SHIFTED); gram_blocks: also block partials of p^dagger out in c->partials
 int hop(bcg_context* c, const bcg_gauge* g, bcg_field* out, const bcg_field* in, bcg::HopMode mode, const bcg_field* p, double c0,

@@ -1,5 +1,9 @@
 // include/blockcg_hip.h, part 2 of 3: the operator -- halo exchange, the stencil launches (kernels_stencil.hip), dirac_op::op
 // (inc/dirac_op.hpp:36-43) with a whole `tmp`, as capacity mode's ring sweep and on half-volume fields, and the gauge API.
+#include <array>
+#include <cassert>
+#include <map>
+
 #include "capi_internal.hpp"
 
 namespace bcg_impl {
@@ -209,13 +213,34 @@ int boundary_tile_list(bcg_context* c, int spb, const int** list, int* n) {
 }
 
 // Profiling only: count the launches of each form of the stencil kernel ("stencil_form_k_hop4c" ...), so that tests
-// and tuning runs can tell which one a lattice shape gets.
-void note_stencil_form(bcg_context* c, int m, int tile_class, const bcg::HopWindow& win, bool plain = false) {
-  if (!c->profiling) return;
-  static const char* names[] = {"stencil_form_general", "stencil_form_k_hop4", "stencil_form_k_hop4c", "stencil_form_k_hop4b"};
-  int form = bcg::hop_kernel_form(m, c->lat, kFastBlocks, c->hop_tune, tile_class, win);
-  if (form == 2 && bcg::hop_uses_bundle(m, c->lat, kFastBlocks, c->hop_tune, tile_class, win, plain)) form = 3;
-  if (form >= 0 && form <= 3) c->prof[names[form]].count += 1;
+// and tuning runs can tell which one a lattice shape gets.  `pl`: the plan that is about to be launched.
+void note_stencil_form(bcg_context* c, const bcg::HopLaunchPlan& pl) {
+  static const char* names[] = {"stencil_form_general", "stencil_form_k_hop4", "stencil_form_k_hop4c", "stencil_form_k_hop4b",
+                                "stencil_form_k_hop4b_checkerboard"};
+  if (c->profiling) c->prof[names[pl.form]].count += 1;
+}
+
+// The plan of one stencil launch on this context (hop_plan.hpp).  lat: c->lat, or its compact form for half fields;
+// a request with fold_target gets the context's fold buffers.  After ensure_scratch: the plan names the pacing counters.
+bcg::HopLaunchPlan plan_stencil(const bcg_context* c, const bcg::LatticeDev& lat, bcg::HopTuning tune, const bcg::HopRequest& rq) {
+  if (c->force_generic) return bcg::HopLaunchPlan();
+  assert(c->hop_tune.sync.counters && c->fold_tickets && "plan_stencil: ensure_scratch comes first");
+  if (rq.fold_target) tune.fold = bcg::GramFold{c->dev_gram, c->fold_tickets};
+  return bcg::hop_plan(lat, kFastBlocks, tune, rq);
+}
+
+// Half-volume fields: the compact lattice (x0 halved) with the half ghost faces -- half the sites at half the offsets,
+// compact in x0 like the field
+static bcg::LatticeDev compact_lattice(const bcg::LatticeDev& full) {
+  bcg::LatticeDev lat = full;
+  lat.L[0] /= 2;
+  lat.V /= 2;
+  for (int mu = 0; mu < 4; ++mu) {
+    if (mu > 0) lat.stride[mu] /= 2;
+    lat.face_sites[mu] /= 2;
+    lat.ghost_off[mu][0] /= 2, lat.ghost_off[mu][1] /= 2;
+  }
+  return lat;
 }
 
 // out = D in  (HOP_PLAIN)  or  out = c0*p - D in  (HOP_SHIFTED).  With gram_blocks != nullptr (m = 16 fast
@@ -228,27 +253,34 @@ int hop(bcg_context* c, const bcg_gauge* g, bcg_field* out, const bcg_field* in,
   if (gram_blocks) *gram_blocks = 0;
   if (gram_folded) *gram_folded = false;
   const bool fast = fast_hop(c, m);
-  // fused Gram product: m = 16 in every form of the specialised stencil; m = 8 in the column-sweep kernel, one launch
-  const bool split_path = fast && bcg::hop_can_split_tiles(m, c->lat) && can_overlap(c);
-  const bool gram = fast && gram_blocks && mode == bcg::HOP_SHIFTED &&
-                    (m == 16 || (m == 8 && !split_path &&
-                                 bcg::hop_kernel_form(m, c->lat, kFastBlocks, c->hop_tune, 0, bcg::HopWindow()) == 2));
-  const char* name = gram ? "hop_shifted_gram" : (mode == bcg::HOP_PLAIN ? "hop" : "hop_shifted");
   if (fast) BCG_TRY(ensure_scratch(c));
+  // pack -> post the exchange -> interior tiles (no ghost reads) -> wait for the exchange -> boundary tiles.
   // BCG_FORCE_TILE_CLASSES=1 (tuning aid): take the two-launch path on an undivided lattice too, where every tile is
   // an interior one, to time the interior-class kernel on one GPU
-  const bool force_classes = c->force_tile_classes;
-  if (fast && bcg::hop_can_split_tiles(m, c->lat) && (can_overlap(c) || (force_classes && !c->distributed))) {
-    // pack -> post the exchange -> interior tiles (no ghost reads) -> wait for the exchange -> boundary tiles
-    if (c->distributed) BCG_TRY(halo_field(c, in, /*split=*/true));
-    bcg::HopTuning tune = c->hop_tune;
+  const bool classes = fast && (can_overlap(c) || (c->force_tile_classes && !c->distributed));
+  bcg::HopTuning tune = c->hop_tune, tb = c->hop_tune;
+  if (classes) {
     tune.blocks = tune.blocks_overlap;  // leave some CUs to the transport's kernels while it runs
-    int nb1, nb2;
-    note_stencil_form(c, m, 1, bcg::HopWindow());
+    BCG_TRY(boundary_tile_list(c, 4 * (64 / m), &tb.boundary_list, &tb.boundary_n));
+  }
+  // Every launch is planned before the first runs.  The fused Gram product (m = 16 in every form, m = 8 in the column forms) is
+  // taken where all of them have it; one whole launch of a column form also sums its partials itself (no reduction launch).
+  bcg::HopLaunchPlan pl, plb;  // the whole launch or the interior class; the boundary class
+  auto plan = [&](bool gram) {
+    pl = plan_stencil(c, c->lat, tune, {m, mode, gram, classes ? 1 : 0, bcg::HopWindow(), gram && !classes && gram_folded});
+    if (classes && tb.boundary_n > 0) plb = plan_stencil(c, c->lat, tb, {m, mode, gram, 2});
+    return pl.form != bcg::HOP_FORM_NONE && (!classes || tb.boundary_n == 0 || plb.form != bcg::HOP_FORM_NONE);
+  };
+  const bool gram = fast && gram_blocks && mode == bcg::HOP_SHIFTED && plan(true);
+  if (fast && !gram) plan(false);
+  const char* name = gram ? "hop_shifted_gram" : (mode == bcg::HOP_PLAIN ? "hop" : "hop_shifted");
+  if (classes) {
+    if (c->distributed) BCG_TRY(halo_field(c, in, /*split=*/true));
+    int nb1, nb2 = 0;
+    note_stencil_form(c, pl);
     {
       ProfScope ps(c, name, alg_bytes(c, m, mode == bcg::HOP_PLAIN ? 2 : 3, 1), hop_flops(c, m, gram));  // both tile classes: counted here
-      nb1 = bcg::launch_hop_fast(c->stream, m, c->lat, g->U, g->Ughost, in->d, c->halo_recv, out->d, mode,
-                                 p ? p->d : nullptr, c0, c->partials, gram, kFastBlocks, tune, /*interior*/ 1);
+      nb1 = bcg::hop_launch(c->stream, pl, g->U, g->Ughost, in->d, c->halo_recv, out->d, p ? p->d : nullptr, c0, c->partials);
     }
     BCG_TRY(check_launch(c, name));
     if (c->distributed) {
@@ -256,35 +288,25 @@ int hop(bcg_context* c, const bcg_gauge* g, bcg_field* out, const bcg_field* in,
       BCG_TRY(exchange_end(c));
     }
     {
-      bcg::HopTuning tb = c->hop_tune;
-      BCG_TRY(boundary_tile_list(c, 4 * (64 / m), &tb.boundary_list, &tb.boundary_n));
-      if (tb.boundary_n == 0) tb.boundary_list = nullptr;  // nothing to do: fall through to an empty class launch
       ProfScope ps(c, "hop_boundary");
-      nb2 = tb.boundary_n == 0 ? 0
-                               : bcg::launch_hop_fast(c->stream, m, c->lat, g->U, g->Ughost, in->d, c->halo_recv, out->d, mode,
-                                                      p ? p->d : nullptr, c0,
-                                                      gram ? c->partials + static_cast<size_t>(nb1) * m * m : c->partials, gram,
-                                                      kFastBlocks, tb, /*boundary*/ 2);
+      if (tb.boundary_n > 0)
+        nb2 = bcg::hop_launch(c->stream, plb, g->U, g->Ughost, in->d, c->halo_recv, out->d, p ? p->d : nullptr, c0,
+                              gram ? c->partials + static_cast<size_t>(nb1) * m * m : c->partials);
     }
     if (gram) *gram_blocks = nb1 + nb2;
     return check_launch(c, "hop_boundary");
   }
   BCG_TRY(halo_field(c, in));
-  if (fast) {
-    note_stencil_form(c, m, 0, bcg::HopWindow(), mode == bcg::HOP_PLAIN);
-    bcg::HopTuning tune = c->hop_tune;
-    // one whole launch of a column form: the kernel's last blocks sum the Gram partials themselves (no reduction launch)
-    const bool fold = gram && gram_folded && bcg::hop_folds_gram(m, c->lat, kFastBlocks, tune, bcg::HopWindow());
-    if (fold) tune.fold = bcg::GramFold{c->dev_gram, c->fold_tickets};
+  if (fast) note_stencil_form(c, pl);
+  {
     ProfScope ps(c, name, alg_bytes(c, m, mode == bcg::HOP_PLAIN ? 2 : 3, 1), hop_flops(c, m, gram));
-    const int nb = bcg::launch_hop_fast(c->stream, m, c->lat, g->U, g->Ughost, in->d, c->halo_recv, out->d, mode,
-                                        p ? p->d : nullptr, c0, c->partials, gram, kFastBlocks, tune, 0);
-    if (gram) *gram_blocks = nb;
-    if (fold) *gram_folded = true;
-  } else {
-    ProfScope ps(c, name, alg_bytes(c, m, mode == bcg::HOP_PLAIN ? 2 : 3, 1), hop_flops(c, m, gram));
-    bcg::launch_hop_generic(c->stream, m, c->lat, g->U, g->Ughost, in->d, c->halo_recv, out->d, mode,
-                            p ? p->d : nullptr, c0);
+    if (fast) {
+      const int nb = bcg::hop_launch(c->stream, pl, g->U, g->Ughost, in->d, c->halo_recv, out->d, p ? p->d : nullptr, c0, c->partials);
+      if (gram) *gram_blocks = nb;
+      if (pl.fold.out) *gram_folded = true;
+    } else {
+      bcg::launch_hop_generic(c->stream, m, c->lat, g->U, g->Ughost, in->d, c->halo_recv, out->d, mode, p ? p->d : nullptr, c0);
+    }
   }
   return check_launch(c, "hop");
 }
@@ -333,23 +355,26 @@ inline int ring_chunk(const bcg_context* c) {
   // ring 32 on a single rank, where the serial form would sweep 30 slices at a time
   return c->ring_chunk_override > 0 && c->ring_chunk_override < most ? c->ring_chunk_override : most;
 }
+// The block partials of all chunks of an x3 sweep side by side (m = 16: the fused Gram product)
+int ensure_chunk_partials(bcg_context* c, int m, int chunks) {
+  BCG_TRY(ensure_scratch(c));
+  const size_t need = static_cast<size_t>(c->hop_tune.blocks > 0 ? c->hop_tune.blocks : kFastBlocks) * chunks * m * m * sizeof(double2);
+  if (m != 16 || need <= c->partials_bytes) return BCG_OK;
+  BCG_TRY(stream_sync(c));
+  (void)hipFree(c->partials);
+  c->partials = nullptr;
+  c->partials_bytes = 0;
+  HIP_TRY(c, hipMalloc(&c->partials, need));
+  c->partials_bytes = need;
+  return BCG_OK;
+}
 // Everything capacity mode allocates for width m: the ring, the block partials of all chunks side by side (the stencil
 // grid stays the tuned one: a smaller grid loses the x3 walk), the face buffers and the copy of the slice-0 faces.
 int ensure_ring_scratch(bcg_context* c, int m) {
   const int R = c->tmp_ring, L3 = c->lat.L[3], C = ring_chunk(c);
   double2*& ring = c->tmp_ring_buf[m];
   if (!ring) HIP_TRY(c, hipMalloc(&ring, static_cast<size_t>(R) * c->lat.stride[3] * 3 * m * sizeof(double2)));
-  BCG_TRY(ensure_scratch(c));
-  const int chunks = (L3 + C - 1) / C;
-  const size_t need = static_cast<size_t>(c->hop_tune.blocks > 0 ? c->hop_tune.blocks : kFastBlocks) * chunks * m * m * sizeof(double2);
-  if (m == 16 && need > c->partials_bytes) {
-    BCG_TRY(stream_sync(c));
-    (void)hipFree(c->partials);
-    c->partials = nullptr;
-    c->partials_bytes = 0;
-    HIP_TRY(c, hipMalloc(&c->partials, need));
-    c->partials_bytes = need;
-  }
+  BCG_TRY(ensure_chunk_partials(c, m, (L3 + C - 1) / C));
   if (c->distributed) {
     const size_t site_bytes = static_cast<size_t>(3) * m * sizeof(double2);
     BCG_TRY(ensure_halo(c, static_cast<size_t>(c->ghost_sites) * site_bytes));
@@ -367,21 +392,37 @@ inline bool half_chunked_path(const bcg_context* c) {
          c->lat.L[3] > half_chunk(c);
 }
 int ensure_half_chunk_scratch(bcg_context* c, int m) {
-  BCG_TRY(ensure_scratch(c));
-  const int C = half_chunk(c), chunks = (c->lat.L[3] + C - 1) / C;
-  const size_t need = static_cast<size_t>(c->hop_tune.blocks > 0 ? c->hop_tune.blocks : kFastBlocks) * chunks * m * m * sizeof(double2);
-  if (m == 16 && need > c->partials_bytes) {  // the block partials of all chunks side by side, as in capacity mode
-    BCG_TRY(stream_sync(c));
-    (void)hipFree(c->partials);
-    c->partials = nullptr;
-    c->partials_bytes = 0;
-    HIP_TRY(c, hipMalloc(&c->partials, need));
-    c->partials_bytes = need;
-  }
+  BCG_TRY(ensure_chunk_partials(c, m, (c->lat.L[3] + half_chunk(c) - 1) / half_chunk(c)));  // (as in capacity mode)
   return ensure_halo(c, static_cast<size_t>(c->ghost_sites) * 3 * m * sizeof(double2));
 }
+// Every stencil launch of the sweep below -- the very windows and modes, with the Gram product where it is asked for --
+// keyed {second stencil?, first slice, slices}.  Half fields: the compact lattice, windows without ring addressing.
+using SweepPlans = std::map<std::array<int, 3>, bcg::HopLaunchPlan>;
+// false: some window of the sweep has no specialised kernel, and the sweep must not start
+bool plan_sweep(const bcg_context* c, const bcg_field* P, const bcg_field* half_tmp, bool want_gram, SweepPlans& sp) {
+  const bool half = half_tmp != nullptr;
+  const int m = P->m, L3 = c->lat.L[3], C = half ? half_chunk(c) : ring_chunk(c);
+  const bcg::LatticeDev lat = half ? compact_lattice(c->lat) : c->lat;
+  bool ok = true;
+  auto add = [&](int second, int lo, int n) {
+    const bcg::HopWindow w{lo, n, half ? 0 : c->tmp_ring, half, half ? (second ? P->parity : half_tmp->parity) : 0};
+    const bcg::HopLaunchPlan pl =
+        plan_stencil(c, lat, c->hop_tune, {m, second ? bcg::HOP_SHIFTED : bcg::HOP_PLAIN, second && want_gram && m == 16, 0, w});
+    ok = ok && pl.form != bcg::HOP_FORM_NONE;
+    sp[{second, lo, n}] = pl;
+  };
+  add(0, L3 - 1, 1);
+  for (int lo = 0, next = 0; lo < L3; lo += C) {  // chunk by chunk: what stage_first and second launch
+    const int hi = lo + C < L3 ? lo + C : L3, last = hi < L3 ? hi : L3 - 1;
+    if (next <= last) add(0, next, last - next + 1);
+    if (hi == L3 && !half) add(0, 0, 1);
+    next = hi + 1;
+    add(1, lo, hi - lo);
+  }
+  return ok;
+}
 int apply_shifted_ring(bcg_context* c, const bcg_gauge* g, double mass, double sigma0, bcg_field* T, const bcg_field* P,
-                       int* gram_blocks, bcg_field* half_tmp = nullptr) {
+                       int* gram_blocks, const SweepPlans& sp, bcg_field* half_tmp = nullptr) {
   const bool half = half_tmp != nullptr;  // P, T: half fields of one parity, half_tmp: the whole tmp of the other
   const int m = P->m, L3 = c->lat.L[3], R = half ? L3 : c->tmp_ring;
   // Overlapped form (ranks that exchange faces, split callbacks present, ring of at least 2 C + 2 slices): the exchange of
@@ -395,20 +436,7 @@ int apply_shifted_ring(bcg_context* c, const bcg_gauge* g, double mass, double s
   double2* const ring = half ? half_tmp->d : c->tmp_ring_buf[m];
   if (gram_blocks) *gram_blocks = 0;
   const bool gram = gram_blocks && m == 16;
-  const bcg::HopTuning& tune = c->hop_tune;
   const size_t site_bytes = static_cast<size_t>(3) * m * sizeof(double2) / (half ? 2 : 1);  // (of the face messages)
-  // half fields: the compact lattice with the half ghost faces' offsets (apply_shifted), windows without ring addressing
-  bcg::LatticeDev lat = c->lat;
-  if (half) {
-    lat.L[0] /= 2;
-    lat.V /= 2;
-    for (int mu = 1; mu < 4; ++mu) lat.stride[mu] /= 2;
-    for (int mu = 0; mu < 4; ++mu) {
-      lat.face_sites[mu] /= 2;
-      lat.ghost_off[mu][0] /= 2;
-      lat.ghost_off[mu][1] /= 2;
-    }
-  }
   const int par_p = half ? P->parity : -1, par_t = half ? half_tmp->parity : -1;
   const int vden = half ? 2 * L3 : L3;  // a window's share of the full local volume
   // Algorithmic link bytes of a launch on HALF fields: every output site needs its four forward links AND the four backward
@@ -416,15 +444,6 @@ int apply_shifted_ring(bcg_context* c, const bcg_gauge* g, double mass, double s
   // stencil reads ALL the lattice's links, 2 x 576 B per output site, where the full-volume one reads each link once for two
   // uses.  (Rounds 3-4 priced one pass: the checkerboard form's "0.44 / 0.49 of the HBM peak" was 27 % / 20 % under-priced.)
   const double kLinkPasses = half ? 2.0 : 1.0;
-  auto window = [&](int lo, int n, int parity_out) {
-    bcg::HopWindow w;
-    w.x3_lo = lo;
-    w.x3_n = n;
-    w.ring = half ? 0 : R;
-    w.cb = half ? 1 : 0;
-    w.cb_parity = half ? parity_out : 0;
-    return w;
-  };
   // The source's faces.  Serial form: one blocking exchange of the whole field.  Overlapped form: nothing blocks -- the
   // faces of the slices the first launches read (the wrap slice L3 - 1 and slices 0 .. C, tmp up to one slice past the
   // first chunk) go first, the rest behind them as a second outstanding exchange that travels while those launches run and is ended
@@ -468,29 +487,22 @@ int apply_shifted_ring(bcg_context* c, const bcg_gauge* g, double mass, double s
   // (a whole tmp keeps its slice 0: nothing is computed twice at the end of the sweep, no faces to put back)
   if (overlap && !half) BCG_TRY(slice0_faces(c, site_bytes, /*save=*/true));
   auto first = [&](int lo, int n) -> int {  // tmp[lo, lo+n) = D P
-    if (half) {
-      if (c->profiling) c->prof["stencil_form_k_hop4b_checkerboard"].count += 1;
-    } else {
-      note_stencil_form(c, m, 0, window(lo, n, 0), /*plain=*/true);
-    }
+    const bcg::HopLaunchPlan& pl = sp.at({0, lo, n});
+    note_stencil_form(c, pl);
     ProfScope ps(c, half ? "hop_half" : "hop_ring", alg_bytes(c, m, 2, kLinkPasses, n, vden), hop_flops(c, m, false, n, vden));
-    const int nb = bcg::launch_hop_fast(c->stream, m, lat, g->U, g->Ughost, P->d, c->halo_recv, ring, bcg::HOP_PLAIN, nullptr,
-                                        0.0, c->partials, false, kFastBlocks, tune, 0, window(lo, n, par_t));
-    if (nb < 0) BCG_FAIL(c, BCG_ERR_UNSUPPORTED, "capacity mode: stencil window rejected");
+    bcg::hop_launch(c->stream, pl, g->U, g->Ughost, P->d, c->halo_recv, ring, nullptr, 0.0, c->partials);
     return check_launch(c, "hop_ring");
   };
   const double c0 = mass * mass + sigma0;
   int total = 0;
   auto second = [&](int lo, int hi) -> int {  // T[lo, hi) from tmp[lo - 1, hi]
     {
-      if (half && c->profiling) c->prof["stencil_form_k_hop4b_checkerboard"].count += 1;
+      const bcg::HopLaunchPlan& pl = sp.at({1, lo, hi - lo});
+      if (half) note_stencil_form(c, pl);
       ProfScope ps(c, half ? (gram ? "hop_half_shifted_gram" : "hop_half_shifted") : (gram ? "hop_shifted_gram_ring" : "hop_shifted_ring"),
                    alg_bytes(c, m, 3, kLinkPasses, hi - lo, vden), hop_flops(c, m, gram, hi - lo, vden));
-      const int nb = bcg::launch_hop_fast(c->stream, m, lat, g->U, g->Ughost, ring, c->halo_recv, T->d, bcg::HOP_SHIFTED, P->d,
-                                          c0, c->partials + static_cast<size_t>(total) * m * m, gram, kFastBlocks, tune, 0,
-                                          window(lo, hi - lo, par_p));
-      if (nb < 0) BCG_FAIL(c, BCG_ERR_UNSUPPORTED, "capacity mode: stencil window rejected");
-      total += nb;
+      total += bcg::hop_launch(c->stream, pl, g->U, g->Ughost, ring, c->halo_recv, T->d, P->d, c0,
+                               c->partials + static_cast<size_t>(total) * m * m);
     }
     return check_launch(c, "hop_shifted_ring");
   };
@@ -560,18 +572,14 @@ int reserve_operator_scratch(bcg_context* c, const bcg_field* like) {
 // self-product.  Everything else -- bcg_dirac_apply, true residuals, capacity mode, half fields, other widths, divided
 // lattices, the row form of the sweep -- keeps the other form's kernels.  BCG_HOP_FACTORED=0 (read at context creation)
 // switches it off.  DESIGN.md section 4.
-static bool factored_pair(const bcg_context* c, int m, double c0, bool want_gram) {
+// (f1, f2: the plans of the two factors, both made before the first runs; the pair is taken only if both are bundle plans)
+static bool factored_pair(const bcg_context* c, int m, double c0, bool want_gram, bool fold, bcg::HopLaunchPlan& f1,
+                          bcg::HopLaunchPlan& f2) {
   if (!c->hop_factored || !want_gram || m != 16 || !(c0 > 0.0) || c->distributed || c->force_tile_classes || !fast_hop(c, m))
     return false;  // (distributed: some direction is divided over ranks)
-  return bcg::hop_uses_bundle(m, c->lat, kFastBlocks, c->hop_tune, 0, bcg::HopWindow(), /*plain=*/true) &&
-         bcg::hop_uses_bundle(m, c->lat, kFastBlocks, c->hop_tune, 0, bcg::HopWindow(), /*plain=*/false);
-}
-
-// whole full-volume fields as the reference writes it: tmp = D P, T = (mass^2 + sigma0) P - D tmp (with P^dagger T where asked)
-static int apply_unfactored(bcg_context* c, const bcg_gauge* g, double mass, double sigma0, bcg_field* T, const bcg_field* P,
-                            bcg_field* tmp, int* gram_blocks, bool* gram_folded) {
-  BCG_TRY(hop(c, g, tmp, P, bcg::HOP_PLAIN, nullptr, 0.0));
-  return hop(c, g, T, tmp, bcg::HOP_SHIFTED, P, mass * mass + sigma0, gram_blocks, gram_folded);
+  f1 = plan_stencil(c, c->lat, c->hop_tune, {m, bcg::HOP_FACT1, false});
+  f2 = plan_stencil(c, c->lat, c->hop_tune, {m, bcg::HOP_FACT2, true, 0, bcg::HopWindow(), fold});
+  return f1.form == bcg::HOP_FORM_BUNDLE && f2.form == bcg::HOP_FORM_BUNDLE;
 }
 
 // T = (mass^2 + sigma0) P - D(D(P))   [op + add(P, sigma0), inc/block_solvers.hpp:134-136]
@@ -586,134 +594,86 @@ int apply_shifted(bcg_context* c, const bcg_gauge* g, double mass, double sigma0
     bcg_field* tmp;
     BCG_TRY(get_tmp_half(c, m, 1 - P->parity, &tmp));
     BCG_TRY(halo_gauge(c, const_cast<bcg_gauge*>(g)));
-    // the bundle sweep in its checkerboard form (m = 16, compact row a multiple of the tile, patch walk), else the generic kernel
+    // the bundle sweep in its checkerboard form (m = 16, 32, compact row a multiple of the tile, patch walk, direction 0 not
+    // divided over ranks), else the generic kernel
     // (algorithmic bytes of these launches: two link passes per half site -- all the lattice's links, see apply_shifted_ring)
-    bcg::LatticeDev latc = c->lat;
-    latc.L[0] /= 2;
-    latc.V /= 2;
-    for (int mu = 1; mu < 4; ++mu) latc.stride[mu] /= 2;
-    for (int mu = 0; mu < 4; ++mu) {  // half ghost faces: half the sites at half the offsets, compact in x0 like the field
-      latc.face_sites[mu] /= 2;
-      latc.ghost_off[mu][0] /= 2;
-      latc.ghost_off[mu][1] /= 2;
-    }
-    // (direction 0 divided over ranks: the compact row's end sites would need the ghost face in one row parity only -- generic kernel)
-    const bool fast = fast_hop(c, m) && (m == 16 || m == 32) && c->ndim == 4 && latc.L[0] > 0 && !c->lat.split[0] &&
-                      bcg::hop_can_split_tiles(m, latc);
+    const bool fast = fast_hop(c, m) && c->lat.L[0] > 1;
+    const bool gram = gram_blocks != nullptr && m == 16;  // the fused product exists at m = 16 (as in the full-volume sweep)
     // direction 3 whole, split exchange available: the sweep in x3 chunks with every exchange overlapped -- provided the
-    // checkerboard bundle sweep takes EVERY window the chunked sweep launches (1, C and C + 1 slices and the last, shorter
-    // chunk).  The chunked sweep has no generic fallback once its first exchange is posted; a tuning that switches the
-    // bundle walk off (BCG_HOP_BUNDLE=0, an odd BCG_HOP_PATCH) or a slice too small for the grid lands in the blocking
-    // path below, which falls back to k_hop_half.
-    bool chunk_windows_ok = fast && half_chunked_path(c);
-    if (chunk_windows_ok) {
-      const int C = half_chunk(c), L3 = c->lat.L[3];
-      for (int n = 1; n <= std::min(C + 1, L3) && chunk_windows_ok; ++n) {
-        bcg::HopWindow w;
-        w.x3_lo = 0;
-        w.x3_n = n;
-        w.cb = 1;
-        chunk_windows_ok = bcg::hop_uses_bundle(m, latc, kFastBlocks, c->hop_tune, 0, w, /*plain=*/true);
-      }
-    }
-    if (chunk_windows_ok) {
-      int nb = 0;
-      BCG_TRY(apply_shifted_ring(c, g, mass, sigma0, T, P, gram_blocks ? &nb : nullptr, tmp));
-      if (gram_blocks) *gram_blocks = nb;
-      return BCG_OK;
-    }
+    // checkerboard bundle sweep takes EVERY window the chunked sweep launches.  The chunked sweep has no generic fallback
+    // once its first exchange is posted; a tuning that switches the bundle walk off (BCG_HOP_BUNDLE=0, an odd
+    // BCG_HOP_PATCH) or a slice too small for the grid lands in the blocking path below, which falls back to k_hop_half.
+    if (fast) BCG_TRY(ensure_scratch(c));
+    SweepPlans sweep;
+    if (fast && half_chunked_path(c) && plan_sweep(c, P, tmp, gram, sweep))
+      return apply_shifted_ring(c, g, mass, sigma0, T, P, gram_blocks, sweep, tmp);
     BCG_TRY(halo_field(c, P));  // (a lattice divided over ranks: the half faces of the source, then below those of tmp)
-    int nb1 = -1, nb2 = -1;
+    bcg::HopLaunchPlan p1, p2;  // both checkerboard launches, planned before the first
     if (fast) {
-      BCG_TRY(ensure_scratch(c));
-      bcg::HopWindow w;
-      w.cb = 1;
-      w.cb_parity = tmp->parity;
-      {
-        ProfScope ps(c, "hop_half", alg_bytes(c, m, 2, 2, 1, 2), hop_flops(c, m, false, 1, 2));
-        nb1 = bcg::launch_hop_fast(c->stream, m, latc, g->U, g->Ughost, P->d, c->halo_recv, tmp->d, bcg::HOP_PLAIN, nullptr, 0.0,
-                                   c->partials, false, kFastBlocks, c->hop_tune, 0, w);
-      }
-      if (nb1 >= 0) {
-        BCG_TRY(check_launch(c, "hop_half"));
-        BCG_TRY(halo_field(c, tmp));
-        const bool gram = gram_blocks != nullptr && m == 16;  // the fused product exists at m = 16 (as in the full-volume sweep)
-        bcg::HopTuning tune = c->hop_tune;
-        const bool fold = gram && gram_folded;
-        if (fold) tune.fold = bcg::GramFold{c->dev_gram, c->fold_tickets};
-        w.cb_parity = T->parity;
-        {
-          ProfScope ps(c, gram ? "hop_half_shifted_gram" : "hop_half_shifted", alg_bytes(c, m, 3, 2, 1, 2), hop_flops(c, m, gram, 1, 2));
-          nb2 = bcg::launch_hop_fast(c->stream, m, latc, g->U, g->Ughost, tmp->d, c->halo_recv, T->d, bcg::HOP_SHIFTED, P->d,
-                                     mass * mass + sigma0, c->partials, gram, kFastBlocks, tune, 0, w);
-        }
-        if (nb2 < 0) BCG_FAIL(c, BCG_ERR_UNSUPPORTED, "half-volume operator: second stencil rejected after the first ran");
-        BCG_TRY(check_launch(c, "hop_half_shifted"));
-        if (gram) {
-          *gram_blocks = nb2;
-          if (fold) *gram_folded = true;
-        }
-        if (c->profiling) c->prof["stencil_form_k_hop4b_checkerboard"].count += 2;
-        return BCG_OK;
-      }
+      const bcg::LatticeDev latc = compact_lattice(c->lat);
+      p1 = plan_stencil(c, latc, c->hop_tune, {m, bcg::HOP_PLAIN, false, 0, {0, 0, 0, 1, tmp->parity}});
+      p2 = plan_stencil(c, latc, c->hop_tune, {m, bcg::HOP_SHIFTED, gram, 0, {0, 0, 0, 1, T->parity}, gram && gram_folded});
     }
+    const bool cb = p1.form != bcg::HOP_FORM_NONE && p2.form != bcg::HOP_FORM_NONE, cb_gram = cb && gram;
+    if (cb) note_stencil_form(c, p1), note_stencil_form(c, p2);
     {
       ProfScope ps(c, "hop_half", alg_bytes(c, m, 2, 2, 1, 2), hop_flops(c, m, false, 1, 2));
-      bcg::launch_hop_half(c->stream, m, c->lat, tmp->parity, g->U, g->Ughost, P->d, c->halo_recv, tmp->d, bcg::HOP_PLAIN, nullptr, 0.0);
+      if (cb) bcg::hop_launch(c->stream, p1, g->U, g->Ughost, P->d, c->halo_recv, tmp->d, nullptr, 0.0, c->partials);
+      else bcg::launch_hop_half(c->stream, m, c->lat, tmp->parity, g->U, g->Ughost, P->d, c->halo_recv, tmp->d, bcg::HOP_PLAIN, nullptr, 0.0);
     }
     BCG_TRY(check_launch(c, "hop_half"));
     BCG_TRY(halo_field(c, tmp));
+    const double c0 = mass * mass + sigma0;
     {
-      ProfScope ps(c, "hop_half_shifted", alg_bytes(c, m, 3, 2, 1, 2), hop_flops(c, m, false, 1, 2));
-      bcg::launch_hop_half(c->stream, m, c->lat, T->parity, g->U, g->Ughost, tmp->d, c->halo_recv, T->d, bcg::HOP_SHIFTED, P->d,
-                           mass * mass + sigma0);
+      ProfScope ps(c, cb_gram ? "hop_half_shifted_gram" : "hop_half_shifted", alg_bytes(c, m, 3, 2, 1, 2), hop_flops(c, m, cb_gram, 1, 2));
+      if (cb) {
+        const int nb = bcg::hop_launch(c->stream, p2, g->U, g->Ughost, tmp->d, c->halo_recv, T->d, P->d, c0, c->partials);
+        if (gram) *gram_blocks = nb;
+        if (p2.fold.out) *gram_folded = true;
+      } else {
+        bcg::launch_hop_half(c->stream, m, c->lat, T->parity, g->U, g->Ughost, tmp->d, c->halo_recv, T->d, bcg::HOP_SHIFTED, P->d, c0);
+      }
     }
     return check_launch(c, "hop_half_shifted");
   }
-  if (capacity_path(c, P->m)) return apply_shifted_ring(c, g, mass, sigma0, T, P, gram_blocks);
+  if (fast_hop(c, P->m)) BCG_TRY(ensure_scratch(c));
+  if (capacity_path(c, P->m)) {
+    SweepPlans sweep;  // (nothing is posted or launched before every window of the sweep has its plan)
+    if (!plan_sweep(c, P, nullptr, gram_blocks != nullptr, sweep)) BCG_FAIL(c, BCG_ERR_UNSUPPORTED, "capacity mode: stencil window rejected");
+    return apply_shifted_ring(c, g, mass, sigma0, T, P, gram_blocks, sweep);
+  }
   bcg_field* tmp;
   BCG_TRY(get_tmp(c, P->m, &tmp));
-  if (factored_pair(c, P->m, mass * mass + sigma0, gram_blocks != nullptr)) {
+  bcg::HopLaunchPlan f1, f2;
+  if (factored_pair(c, P->m, mass * mass + sigma0, gram_blocks != nullptr, gram_folded != nullptr, f1, f2)) {
     // mu * mu differs from mass^2 + sigma0 by at most one ulp: a perturbation of sigma0 by 1e-16 (mass^2 + sigma0), about
     // 1e-22 at mass 1e-3 -- far below the rounding of the operator itself (1e-16 |D^2 P|, |D^2| up to 16)
     const double mu = std::sqrt(mass * mass + sigma0);
     BCG_TRY(halo_gauge(c, const_cast<bcg_gauge*>(g)));
-    BCG_TRY(ensure_scratch(c));
-    bcg::HopTuning tune = c->hop_tune;
-    int nb1;
+    if (c->profiling) c->prof["stencil_form_factored_pair"].count += 1;
+    note_stencil_form(c, f1);
     {  // W = (mu - D) P: the plain hop's streams
       ProfScope ps(c, "hop", alg_bytes(c, P->m, 2, 1), hop_flops(c, P->m, false));
-      nb1 = bcg::launch_hop_fast(c->stream, P->m, c->lat, g->U, g->Ughost, P->d, c->halo_recv, tmp->d, bcg::HOP_FACT1, nullptr, mu,
-                                 c->partials, false, kFastBlocks, tune, 0);
-      if (nb1 < 0) ps.cancel();
+      bcg::hop_launch(c->stream, f1, g->U, g->Ughost, P->d, c->halo_recv, tmp->d, nullptr, mu, c->partials);
     }
-    // the launcher declined where factored_pair() expected it to accept: nothing has run, the other form below serves
-    if (nb1 < 0) return apply_unfactored(c, g, mass, sigma0, T, P, tmp, gram_blocks, gram_folded);
-    if (c->profiling) c->prof["stencil_form_factored_pair"].count += 1;
-    note_stencil_form(c, P->m, 0, bcg::HopWindow(), /*plain=*/true);
     BCG_TRY(check_launch(c, "hop"));
     // T = (mu + D) W and the partials of W^dagger W = P^dagger T; tmp (= W) is read by this launch alone.
     // The kernel forms the self-product in two real products and stores Im G = C - C^T (mfma_common.hpp:
     // gram_self_step): what it sums is Hermitian with a real diagonal already, so for this path finish_gram's mirror of the
     // lower triangle and phase_A's drop of Im G_ii (gram_self below) change no bit.  They stay for the other forms.
-    const bool fold = gram_folded && bcg::hop_folds_gram(P->m, c->lat, kFastBlocks, tune, bcg::HopWindow());
-    if (fold) tune.fold = bcg::GramFold{c->dev_gram, c->fold_tickets};
-    int nb;
+    note_stencil_form(c, f2);
     {
-      note_stencil_form(c, P->m, 0, bcg::HopWindow());
       ProfScope ps(c, "hop_shifted_gram", alg_bytes(c, P->m, 2, 1), hop_flops(c, P->m, true));
-      nb = bcg::launch_hop_fast(c->stream, P->m, c->lat, g->U, g->Ughost, tmp->d, c->halo_recv, T->d, bcg::HOP_FACT2, nullptr, mu,
-                                c->partials, true, kFastBlocks, tune, 0);
+      *gram_blocks = bcg::hop_launch(c->stream, f2, g->U, g->Ughost, tmp->d, c->halo_recv, T->d, nullptr, mu, c->partials);
     }
-    if (nb < 0) BCG_FAIL(c, BCG_ERR_UNSUPPORTED, "factored stencil pair: second factor rejected after the first ran");
-    *gram_blocks = nb;
-    if (fold) *gram_folded = true;
+    if (f2.fold.out) *gram_folded = true;
     if (gram_self) *gram_self = true;
     return check_launch(c, "hop_shifted_gram");
   }
-  return apply_unfactored(c, g, mass, sigma0, T, P, tmp, gram_blocks, gram_folded);
+  // as the reference writes it: tmp = D P, T = (mass^2 + sigma0) P - D tmp (with P^dagger T where asked)
+  BCG_TRY(hop(c, g, tmp, P, bcg::HOP_PLAIN, nullptr, 0.0));
+  return hop(c, g, T, tmp, bcg::HOP_SHIFTED, P, mass * mass + sigma0, gram_blocks, gram_folded);
 }
-
 
 }  // namespace bcg_impl
 

@@ -371,25 +371,27 @@ int bcg_true_residuals(bcg_context* c, const bcg_gauge* g, double mass, bcg_fiel
     // One pass where the bundle stencil applies (m = 16, whole-field tmp): tmp = D X_s, then the second stencil
     // forms (mass^2 + sigma_s) X_s - D tmp - B in registers and accumulates its Gram product; AX is never written
     // (5 field passes + 2 link passes instead of 9 + 2).
-    if (m == 16 && B->parity < 0 && fast_hop(c, m) && !capacity_path(c, m) &&
-        bcg::hop_uses_bundle(m, c->lat, kFastBlocks, c->hop_tune, 0, bcg::HopWindow())) {
+    // The fused launch is planned before anything runs: where it has no kernel, the unfused path below serves at once.
+    bcg::HopLaunchPlan fused;
+    if (m == 16 && B->parity < 0 && fast_hop(c, m) && !capacity_path(c, m)) {
+      BCG_TRY(ensure_scratch(c));
+      fused = plan_stencil(c, c->lat, c->hop_tune, {m, bcg::HOP_RESID, true});
+    }
+    if (fused.form != bcg::HOP_FORM_NONE) {
       bcg_field* tmp;
       BCG_TRY(get_tmp(c, m, &tmp));
       BCG_TRY(hop(c, g, tmp, X[s], bcg::HOP_PLAIN, nullptr, 0.0));
       BCG_TRY(halo_field(c, tmp));
-      BCG_TRY(ensure_scratch(c));
       int nb;
       {
         ProfScope ps(c, "hop_residual", alg_bytes(c, m, 3, 1));  // reads tmp, X_s, B and the links; writes nothing
-        nb = bcg::launch_hop_fast(c->stream, m, c->lat, g->U, g->Ughost, tmp->d, c->halo_recv, const_cast<double2*>(B->d),
-                                  bcg::HOP_RESID, X[s]->d, mass * mass + sigma[s], c->partials, true, kFastBlocks, c->hop_tune, 0);
+        nb = bcg::hop_launch(c->stream, fused, g->U, g->Ughost, tmp->d, c->halo_recv, const_cast<double2*>(B->d), X[s]->d,
+                             mass * mass + sigma[s], c->partials);
       }
-      if (nb > 0) {
-        BCG_TRY(check_launch(c, "hop_residual"));
-        BCG_TRY(finish_gram(c, m, nb, r2, true));
-        for (int i = 0; i < m; ++i) res_out[s * m + i] = std::sqrt(r2(i, i).real() / b2(i, i).real());
-        continue;
-      }
+      BCG_TRY(check_launch(c, "hop_residual"));
+      BCG_TRY(finish_gram(c, m, nb, r2, true));
+      for (int i = 0; i < m; ++i) res_out[s * m + i] = std::sqrt(r2(i, i).real() / b2(i, i).real());
+      continue;
     }
     if (!AX) BCG_TRY(pool.make(m, &AX));
     BCG_TRY(apply_shifted(c, g, mass, sigma[s], AX, X[s]));  // op + add(X_s, sigma_s) in one pass

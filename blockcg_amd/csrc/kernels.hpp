@@ -55,12 +55,12 @@ enum HopMode { HOP_PLAIN = 0, HOP_SHIFTED = 1, HOP_RESID = 2, HOP_FACT1 = 3, HOP
 // HOP_SHIFTED: out = c0 * p - D in                 (second D of op fused with K2 and K3)
 // HOP_RESID  : nothing is written; r = c0 * p - D in - b with b passed in `out`'s place, and the block partials of
 //              r^dagger r are left like a fused Gram product (the reference's residual check, test/solvers.cpp:105-111,
-//              as one pass; specialised bundle kernel at m = 16 only, launch_hop_fast returns -1 otherwise)
+//              as one pass; specialised bundle kernel at m = 16 only, hop_plan declines otherwise)
 // HOP_FACT1 / HOP_FACT2: the two factors of c0^2 - D^2 = (c0 + D)(c0 - D), D anti-Hermitian:
 //              FACT1: out = c0 * in - D in;  FACT2: out = c0 * in + D in, with the block partials of in^dagger in (the
 //              Gram product of FACT1's input with FACT2's output).  No `p`: the shift term is the stencil's own input,
 //              taken from the row the kernel already holds.  Whole-field launches of the bundle kernel at m = 16 only,
-//              launch_hop_fast returns -1 otherwise
+//              hop_plan declines otherwise
 void launch_hop_generic(hipStream_t s, int m, const LatticeDev& lat, const double2* U, const double2* Ughost,
                         const double2* in, const double2* ghost, double2* out, HopMode mode, const double2* p,
                         double c0);

@@ -61,7 +61,7 @@ struct HopSync {
   bool column_walk = true;       // use k_hop4c (scalar row pointers, column sweep) where the walk allows it
   int bundle_walk = 1;           // k_hop4b (2 x 2 column bundles sharing rows through LDS) for whole launches: 0 off, 1 at
                                  // m = 16 and 32 and for the plain hop at m = 8, 2 for every launch at m = 8 too
-  int bundle_window = 4;         // pacing window of k_hop4b (0 = unpaced; < 0: |value|, also where bundle_paced() would not pace).  Round 3, links by LDS-DMA: windows 4..12 take the
+  int bundle_window = 4;         // pacing window of k_hop4b (0 = unpaced; < 0: |value|, also where hop_plan.cpp's bundle_paced() would not pace).  Round 3, links by LDS-DMA: windows 4..12 take the
                                  // same time as the unpaced sweep (10.50 vs 10.46 ms, 12.00 vs 12.06 ms at 64^4) and move
                                  // 20 % fewer bytes past the L2 (45.7 vs 57.2 GB, 59.0 vs 72.0 GB); window 3 costs 2 %
 };
@@ -99,19 +99,8 @@ struct HopWindow {
   int cb = 0, cb_parity = 0;
 };
 
-// Stencil; with gram (m = 16, HOP_SHIFTED) also writes partials of p^dagger out.  Returns blocks used.
-int launch_hop_fast(hipStream_t s, int m, const LatticeDev& lat, const double2* U, const double2* Ughost,
-                    const double2* in, const double2* ghost, double2* out, HopMode mode, const double2* p, double c0,
-                    double2* partials, bool gram, int max_blocks, const HopTuning& tune, int tile_class,
-                    const HopWindow& win = HopWindow());
-// true when launch_hop_fast can process interior (tile_class 1) and boundary (2) tiles in separate launches
+// Lattices the specialised 4-D stencil takes at width m (hop_plan.hpp plans and launches it), in whole launches or with
+// interior (tile_class 1) and boundary (2) tiles in separate launches
 bool hop_can_split_tiles(int m, const LatticeDev& lat);
-// Which kernel launch_hop_fast will use: 0 none (the caller runs k_hop_generic), 1 k_hop4 (tile counter), 2 k_hop4c (column sweep), -1 rejected
-int hop_kernel_form(int m, const LatticeDev& lat, int max_blocks, const HopTuning& tune, int tile_class, const HopWindow& win);
-// true when a whole launch (tile class 0) with the fused Gram product folds its partials itself (HopTuning::fold honoured)
-bool hop_folds_gram(int m, const LatticeDev& lat, int max_blocks, const HopTuning& tune, const HopWindow& win);
-// true when form 2 is served by k_hop4b (2 x 2 column bundles) rather than k_hop4c
-bool hop_uses_bundle(int m, const LatticeDev& lat, int max_blocks, const HopTuning& tune, int tile_class, const HopWindow& win,
-                     bool plain = false);
 
 }  // namespace bcg

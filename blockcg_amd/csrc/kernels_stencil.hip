@@ -2,6 +2,10 @@
 // widths m = 8, 16, 32 -- k_hop4 / k_hop4c (4-D tile and column forms, tile classes of the split
 // halo exchange) and k_hop4b (2 x 2 column bundles: the software-pipelined, broadcast-link step; ring windows; the
 // checkerboard form for half-volume fields) -- with their launchers.  Shared helpers: mfma_common.hpp.
+#include <cassert>
+
+#include "hop_layout.hpp"
+#include "hop_plan.hpp"
 #include "mfma_common.hpp"
 
 namespace bcg {
@@ -23,13 +27,10 @@ __device__ __forceinline__ unsigned lds_addr_of(const void* p) {
 // 11.90-12.16), and the plain form issues its vector-memory instructions grouped (SPREAD 0; the shifted forms: SPREAD below).
 // PIPE: the software-pipelined schedule of the bundle sweep (m = 16, 32; full-lattice form): every global access of a step is
 // an operation hipcc does not see, issued where it pays and retired by hand-counted s_waitcnt -- see "PIPE" in hop4b_body.
-// -DBCG_HOP4B_PIPE=0 is the A/B build: the step of rounds 1-3 (still what m = 8 and the residual form run).
+// -DBCG_HOP4B_PIPE=0 is the A/B build: the step of rounds 1-3 (still what m = 8 and the residual form run); hop_layout.hpp.
 // The tuning builds of round 3 (the +x3 row by LDS-DMA, rows one step ahead, scheduling-barrier masks, write-through stores,
 // non-temporal link DMAs, the ablations of profiles/r03_stencil_ablation.txt, the carried-address check) have been removed:
 // their results are recorded in profiles/r03_stencil_*.txt and DESIGN_HISTORY.md, and PIPE supersedes what they explored.
-#ifndef BCG_HOP4B_PIPE
-#define BCG_HOP4B_PIPE 1
-#endif
 // SPREAD (bit mask per form): parts of the step's vector-memory instructions issued one or two at a time behind the 24-FMA
 // units instead of in a group behind a direction -- 1: the row DMAs, 2: the link DMAs, 4: the second group of next-step
 // rows behind direction 2 (the waits only need rows first, p second; the rest may come in any order).  Measured at 64^4,
@@ -271,8 +272,8 @@ __global__ void __launch_bounds__(256) k_hop4(LatticeDev lat, const double2* __r
   constexpr int SPW = 64 / M;
   constexpr int SPB = 4 * SPW;
   constexpr int NW = 4;
-  constexpr int NF = (SPB + 1) * 36;   // forward links of sites -1 .. SPB-1 (all 4 directions)
-  constexpr int NB = 3 * SPB * 9;      // backward links of directions 1..3
+  constexpr int NF = hop4_fwd_links(M);   // forward links of sites -1 .. SPB-1 (all 4 directions)
+  constexpr int NB = hop4_bwd_links(M);   // backward links of directions 1..3
   constexpr int STAGE = NF + NB;       // double2 per LDS stage
   constexpr int RF = (SPB * 36 + 255) / 256;  // register slots per thread for the forward run
   extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -581,8 +582,8 @@ __device__ __forceinline__ void hop4c_body(const LatticeDev& lat, const double2*
   constexpr int SPW = 64 / M;
   constexpr int SPB = 4 * SPW;
   constexpr int NW = 4;
-  constexpr int NF = (SPB + 1) * 36;
-  constexpr int NB = 3 * SPB * 9;
+  constexpr int NF = hop4_fwd_links(M);
+  constexpr int NB = hop4_bwd_links(M);
   constexpr int STAGE = NF + NB;
   constexpr int RF = (SPB * 36 + 255) / 256;
   constexpr int RBM = (SPB * 9 + 255) / 256;
@@ -934,9 +935,7 @@ k_hop4c_interior(LatticeDev lat, const double2* __restrict__ U, const double2* _
 // of k_hop4c; the interior / boundary tile classes of the split halo exchange stay with k_hop4c.  Same arithmetic per site
 // and the same order of the four directions, so results are bit-identical to k_hop4c.
 // ---------------------------------------------------------------------------------------------------
-// Two link images per wave (partner waves read each other's forward links) where two blocks per CU still fit the 160 KB
-// of LDS: m = 16 (73.7 KB per block) and m = 32 (70 KB); at m = 8 (two images: 100 KB) one image, own links only.
-__host__ __device__ constexpr bool hop4b_share_images(int m) { return m >= 16; }
+// (hop4b_share_images and the LDS layout: hop_layout.hpp, shared with the planner)
 
 template <int M, int MODE, bool GRAM, bool RING, bool CB = false>
 __device__ __forceinline__ void hop4b_body(const LatticeDev& lat, const double2* __restrict__ U,
@@ -973,9 +972,9 @@ __device__ __forceinline__ void hop4b_body(const LatticeDev& lat, const double2*
   static_assert(!CB || (!RING && !RESID), "checkerboard form: whole-field launches only");
   constexpr int SPW = 64 / M;              // sites per wave = tile extent in x0
   constexpr int NW = 4;
-  constexpr int CS = (SPW + 2) * 3 * M;    // one wave's row slot: halo site, SPW sites, halo site (complex numbers)
-  constexpr int NFW = (SPW + 1) * 36;      // link image of a wave: slot of the site to the left (U_0 only), forward links
-  constexpr int NBW = (CB ? 4 : 3) * SPW * 9;  // ... backward links, directions 1..3 (CB: and direction 0, behind them)
+  constexpr int CS = hop4b_row_slot(M);    // one wave's row slot: halo site, SPW sites, halo site (complex numbers)
+  constexpr int NFW = hop4b_fwd_links(M);  // link image of a wave: slot of the site to the left (U_0 only), forward links
+  constexpr int NBW = hop4b_bwd_links(M, CB);  // ... backward links, directions 1..3 (CB: and direction 0, behind them)
   constexpr int LSTAGE = NFW + NBW;
   constexpr int RFW = (SPW * 36 + 63) / 64;
   constexpr int RBK = (SPW * 9 + 63) / 64;
@@ -2137,261 +2136,80 @@ template __global__ void k_hop4c<16, HOP_SHIFTED, true, 0, false>(LatticeDev, co
 #else
 }  // namespace
 
-bool hop_fast_width(int m) { return m == 8 || m == 16 || m == 32; }
-bool hop_can_split_tiles(int m, const LatticeDev& lat) {
-  const int spb = 4 * (64 / m);
-  return hop_fast_width(m) && lat.ndim == 4 && lat.L[0] % spb == 0 && lat.V < (int64_t(1) << 31) - 2 * lat.stride[3];
-}
-// What one launch of the specialised stencil will do (shared by the launcher and hop_kernel_form).
-struct HopPlan {
-  bool valid = false;
-  bool column = false;  // k_hop4c (column sweep, scalar row pointers) instead of k_hop4
-  bool list = false;    // k_hop4 over an explicit tile list (boundary class)
-  int ntiles = 0, grid = 0;
-  HopWalk hw{};
-  HopWindow win{};
-};
-static HopPlan plan_hop4(int m, const LatticeDev& lat, int max_blocks, const HopTuning& tune, int cls, HopWindow win) {
-  HopPlan pl;
-  const int SPB = 4 * (64 / m);
-  // patch extent in x0: one tile unless set (a patch slice then has p1*p2 = 64 tiles = the blocks of an XCD at every width)
-  const int walk = tune.patch_walk ? 3 : 0, p0 = tune.patch[0] > 0 ? tune.patch[0] : SPB, p1 = tune.patch[1], p2 = tune.patch[2];
-  if (win.x3_n <= 0) {
-    win.x3_lo = 0;
-    win.x3_n = lat.L[3];
-  }
-  if (win.x3_lo < 0 || win.x3_lo + win.x3_n > lat.L[3]) return pl;
-  // ring addressing: whole tiles only (no interior/boundary split), direction 3 undivided, ring | L3
-  if (win.ring > 0 && (cls != 0 || lat.split[3] || win.ring < 3 || lat.L[3] % win.ring != 0)) return pl;
-  pl.win = win;
-  pl.ntiles = static_cast<int>(lat.V / lat.L[3] * win.x3_n / SPB);
-  const bool ok3 = walk == 3 && p0 > 0 && p1 > 0 && p2 > 0 && p0 % SPB == 0 && lat.L[0] % p0 == 0 && lat.L[1] % p1 == 0 &&
-                   lat.L[2] % p2 == 0 && pl.ntiles % 8 == 0 && max_blocks % 8 == 0 && pl.ntiles / 8 >= max_blocks / 8;
-  pl.hw = HopWalk{lat.L[0], lat.L[1], lat.L[2], 0, nullptr, 0, 0, 0, nullptr, 0, GramFold{}};  // lexicographic = one patch
-  if (ok3) pl.hw = HopWalk{p0, p1, p2, 1, nullptr, 0, 0, 0, nullptr, 0, GramFold{}};
-  if (ok3 && tune.super_patch && (lat.L[0] / p0) % 2 == 0 && (lat.L[1] / p1) % 2 == 0 && (lat.L[2] / p2) % 2 == 0) pl.hw.super = 1;
-  if (cls == 2 && tune.boundary_list != nullptr) {  // the boundary class from its tile list, round-robin
-    pl.hw = HopWalk{lat.L[0], lat.L[1], lat.L[2], 0, nullptr, 0, 0, 0, tune.boundary_list, tune.boundary_n, GramFold{}};
-    pl.grid = tune.boundary_n < max_blocks ? tune.boundary_n : max_blocks;
-    pl.column = false;
-    pl.list = true;
-    pl.valid = true;
-    return pl;
-  }
-  pl.grid = pl.ntiles < max_blocks ? pl.ntiles : max_blocks;
-  if (pl.hw.xcd_split) pl.grid &= ~7;
-  // column form of the walk: one block per tile of a patch slice, whole patches per XCD class
-  pl.column = tune.sync.column_walk && pl.hw.xcd_split && pl.grid / 8 == (p0 / SPB) * p1 * p2 &&
-              ((lat.L[0] / p0) * (lat.L[1] / p1) * (lat.L[2] / p2)) % 8 == 0;
-  if (pl.column && tune.sync.window > 0 && tune.sync.counters != nullptr) {
-    const int steps = pl.ntiles / pl.grid;  // tiles per block (every block has the same number)
-    if (steps <= tune.sync.stride) {
-      pl.hw.sync = tune.sync.counters;
-      pl.hw.sync_window = tune.sync.window;
-      pl.hw.sync_stride = tune.sync.stride;
-      pl.hw.sync_limit = tune.sync.limit_ticks;
-    }
-  }
-  pl.valid = true;
-  return pl;
-}
-
-// k_hop4b (2 x 2 column bundles) serves whole launches of the column form whose patches are made of whole bundle tiles
-// (at m = 8 the plain form only unless bundle_walk = 2: measured at 32^4, 0.36 vs 0.41 ms plain, 0.50 vs 0.44 ms with the Gram product)
-static bool bundle_ok(int m, const LatticeDev& lat, const HopTuning& tune, const HopPlan& pl, int cls, bool plain) {
-  const int spw = 64 / m;
-  // short x3 windows (capacity ring 8: 6 slices) do not repay the bundle's column prologue -- two row loads before the
-  // first step -- (measured at 64^3 x 128: ring 8 144.6 vs 142.6 ms per iteration, ring 16 140.4 vs 141.1 ms)
-  if (pl.win.ring > 0 && pl.win.x3_n < 10 && tune.sync.bundle_walk < 2) return false;
-  return pl.valid && pl.column && tune.sync.bundle_walk && cls == 0 && (m != 8 || plain || tune.sync.bundle_walk > 1) &&
-         lat.L[1] % 2 == 0 && lat.L[2] % 2 == 0 && pl.hw.p1 % 2 == 0 && pl.hw.p2 % 2 == 0 && pl.hw.p0 % spw == 0 &&
-         (pl.hw.p0 / spw) * (pl.hw.p1 / 2) * (pl.hw.p2 / 2) == pl.grid / 8;
-}
-
-// The bundle sweep is paced only where it is free: whole-field launches of at least 256 steps per block.  Measured
-// (profiles/r03_pacing_ab_other_shapes.txt): at 64^4 (2048 steps) paced = unpaced in time with 20 % less fabric traffic; at
-// 32^4, m = 8 (64 steps) the paced plain hop takes 0.376 vs 0.360 ms; capacity-mode windows (15-30 slices) 22.3 vs 21.6 ms.
-// BCG_HOP_BUNDLE_SYNC < 0 forces pacing with window |value| everywhere (tests).
-// Round 4: with the software-pipelined step (m = 16, 32) the capacity-mode windows gain from pacing too -- 64^3 x 128 share, ring
-// 32: hop_ring 18.2 vs 18.8 ms, with the Gram product 23.8 vs 24.4, 107.6-108.1 vs 108.8 ms per iteration
-// (profiles/r04_cap128_pacing_ab.txt) -- so there only the step count decides.
-static bool bundle_paced(int m, int ntiles, int grid, const HopWindow& win) {
-  const bool pipelined = BCG_HOP4B_PIPE != 0 && hop4b_share_images(m) && win.cb == 0;
-  return (win.ring == 0 || pipelined) && grid > 0 && ntiles / grid >= 256;
-}
-
+// One width's part of hop_launch: the instantiation the plan names (exactly the set instantiated: the fused Gram product
+// exists for HOP_SHIFTED at m = 16 and, in the column and bundle forms, at m = 8; RESID and the factored pair at m = 16).
 template <int M>
-static int launch_hop4(hipStream_t s, const LatticeDev& lat, const double2* U, const double2* Ughost, const double2* in,
-                       const double2* ghost, double2* out, HopMode mode, const double2* p, double c0, double2* partials,
-                       bool gram, int max_blocks, const HopTuning& tune, int cls, const HopWindow& win_in) {
-  constexpr int SPB = 4 * (64 / M);
-  const HopPlan pl = plan_hop4(M, lat, max_blocks, tune, cls, win_in);
-  if (!pl.valid) return -1;
-  const int grid = pl.grid, ntiles = pl.ntiles;
-  HopWalk hw = pl.hw;
-  if (gram && pl.column && cls == 0) hw.fold = tune.fold;  // whole launches of the column forms fold their Gram partials
-  const HopWindow win = pl.win;
-  const size_t lds_g = gram ? sizeof(double) * 4 * 8 * 64 : 0;
-  if (pl.list && grid == 0) return 0;  // no boundary tiles
-  const int cls_t = pl.list ? 0 : cls;  // the list holds exactly the launch's tiles: no class filter in the kernel
-  // the factored pair exists in the bundle sweep only: whole full-volume fields at m = 16, FACT2 with its Gram product
-  const bool fact = mode == HOP_FACT1 || mode == HOP_FACT2;
-  if (fact && (M != 16 || win.cb || win.ring > 0 || cls != 0 || gram != (mode == HOP_FACT2))) return -1;
-  // checkerboard form (half-volume fields): the bundle sweep at m = 16, 32 on a lattice whose direction 0 is not divided
-  // over ranks (lat: the compact lattice, with the half ghost faces' offsets), or nothing (the caller then runs the generic
-  // half-volume kernel)
-  if (win.cb) {
-    // m = 16 and 32: the widths with two link images per wave (the DMA needs the one that is not being read)
-    // (direction 0 divided: a compact row's end sites would read the ghost face in one row parity only -- not built)
-    if (!hop4b_share_images(M) || (gram && M != 16) || mode == HOP_RESID || win.ring > 0 || cls != 0 || lat.split[0] ||
-        !bundle_ok(M, lat, tune, pl, cls, true))
-      return -1;
-    constexpr int MC = hop4b_share_images(M) ? M : 16;  // (never launched for the other widths)
-    HopWalk hwb = hw;
-    if (tune.sync.bundle_window != 0 && hw.sync && (tune.sync.bundle_window < 0 || bundle_paced(M, ntiles, grid, win)))
-      hwb.sync_window = tune.sync.bundle_window < 0 ? -tune.sync.bundle_window : tune.sync.bundle_window;
-    else hwb.sync = nullptr;
-    if (hwb.sync) (void)hipMemsetAsync(hwb.sync, 0, sizeof(unsigned) * 8 * hwb.sync_stride, s);
-    constexpr int SPWc = 64 / MC;
-    const size_t lds_u = sizeof(double2) * (2 * 4 * ((SPWc + 2) * 3 * MC) + 2 * 4 * ((SPWc + 1) * 36 + 4 * SPWc * 9));
-    const size_t lds = lds_u > lds_g ? lds_u : lds_g;
-#define BCG_LAUNCH4B_CB(MM, MD, GR)                                                                                      \
-  do {                                                                                                              \
-    allow_lds(k_hop4b<MM, MD, GR, false, true>, lds);                                                               \
-    hipLaunchKernelGGL((k_hop4b<MM, MD, GR, false, true>), dim3(grid), dim3(256), lds, s, lat, U, Ughost, in, ghost, out, p, \
-                       c0, partials, hwb, win);                                                                     \
+static void launch_hop4(hipStream_t s, const HopLaunchPlan& pl, const HopWalk& hw, const double2* U, const double2* Ughost,
+                        const double2* in, const double2* ghost, double2* out, const double2* p, double c0, double2* partials) {
+  const HopWindow& win = pl.win;
+  const bool gram = pl.req.gram, ring = win.ring > 0;
+  const int mode = pl.req.mode, ntiles = pl.ntiles, cls = pl.tile_list ? 0 : pl.req.tile_class;  // (a list holds exactly the launch's tiles)
+#define BCG_LAUNCH(K, ...)                                                                                           \
+  do {                                                                                                               \
+    allow_lds(K, pl.lds);                                                                                            \
+    hipLaunchKernelGGL(K, dim3(pl.grid), dim3(256), pl.lds, s, pl.lat, U, Ughost, in, ghost, out, p, c0, partials, __VA_ARGS__); \
   } while (0)
-    if (mode == HOP_PLAIN) BCG_LAUNCH4B_CB(MC, HOP_PLAIN, false);
-    else if (gram) BCG_LAUNCH4B_CB(16, HOP_SHIFTED, true);
-    else BCG_LAUNCH4B_CB(MC, HOP_SHIFTED, false);
-#undef BCG_LAUNCH4B_CB
-    return grid;
-  }
-  // k_hop4b: the column sweep over 2 x 2 bundles (whole launches only: the tile classes stay with k_hop4c)
-  if (bundle_ok(M, lat, tune, pl, cls, mode == HOP_PLAIN)) {
-    HopWalk hwb = hw;  // pacing of the bundle sweep: its own window, long whole-field sweeps only (bundle_paced)
-    if (tune.sync.bundle_window != 0 && hw.sync && (tune.sync.bundle_window < 0 || bundle_paced(M, ntiles, grid, win)))
-      hwb.sync_window = tune.sync.bundle_window < 0 ? -tune.sync.bundle_window : tune.sync.bundle_window;
-    else hwb.sync = nullptr;
-    if (hwb.sync) (void)hipMemsetAsync(hwb.sync, 0, sizeof(unsigned) * 8 * hwb.sync_stride, s);
-    constexpr int SPW = 64 / M;
-    const size_t lds_u = sizeof(double2) * (2 * 4 * ((SPW + 2) * 3 * M) +
-                                            (hop4b_share_images(M) ? 2 : 1) * 4 * ((SPW + 1) * 36 + 3 * SPW * 9));
-    const size_t lds = lds_u > lds_g ? lds_u : lds_g;
-#define BCG_LAUNCH4B(MM, MD, GR, RG)                                                                                \
-  do {                                                                                                             \
-    allow_lds(k_hop4b<MM, MD, GR, RG>, lds);                                                                       \
-    hipLaunchKernelGGL((k_hop4b<MM, MD, GR, RG>), dim3(grid), dim3(256), lds, s, lat, U, Ughost, in, ghost, out, p, \
-                       c0, partials, hwb, win);                                                                     \
+  if (pl.form == HOP_FORM_BUNDLE_CB) {
+    constexpr int MC = hop4b_share_images(M) ? M : 16;  // (never planned for the other widths)
+    if (mode == HOP_PLAIN) BCG_LAUNCH((k_hop4b<MC, HOP_PLAIN, false, false, true>), hw, win);
+    else if (gram) BCG_LAUNCH((k_hop4b<16, HOP_SHIFTED, true, false, true>), hw, win);
+    else BCG_LAUNCH((k_hop4b<MC, HOP_SHIFTED, false, false, true>), hw, win);
+  } else if (pl.form == HOP_FORM_BUNDLE) {
+#define BCG_LAUNCH4B_R(MM, MD, GR)                                        \
+  do {                                                                    \
+    if (ring) BCG_LAUNCH((k_hop4b<MM, MD, GR, true>), hw, win);           \
+    else BCG_LAUNCH((k_hop4b<MM, MD, GR, false>), hw, win);               \
   } while (0)
-#define BCG_LAUNCH4B_R(MM, MD, GR)                      \
-  do {                                                  \
-    if (win.ring > 0) BCG_LAUNCH4B(MM, MD, GR, true);   \
-    else BCG_LAUNCH4B(MM, MD, GR, false);               \
-  } while (0)
-    if (mode == HOP_RESID) {
-      if (M != 16 || !gram || win.ring > 0) return -1;
-      BCG_LAUNCH4B(16, HOP_RESID, true, false);
-    } else if (mode == HOP_FACT1) BCG_LAUNCH4B(16, HOP_FACT1, false, false);
-    else if (mode == HOP_FACT2) BCG_LAUNCH4B(16, HOP_FACT2, true, false);
-    else if (gram && M == 16 && mode == HOP_SHIFTED) BCG_LAUNCH4B_R(16, HOP_SHIFTED, true);
-    else if (gram && M == 8 && mode == HOP_SHIFTED) BCG_LAUNCH4B_R(8, HOP_SHIFTED, true);
+    if (mode == HOP_RESID) BCG_LAUNCH((k_hop4b<16, HOP_RESID, true, false>), hw, win);
+    else if (mode == HOP_FACT1) BCG_LAUNCH((k_hop4b<16, HOP_FACT1, false, false>), hw, win);
+    else if (mode == HOP_FACT2) BCG_LAUNCH((k_hop4b<16, HOP_FACT2, true, false>), hw, win);
+    else if (gram && M == 16) BCG_LAUNCH4B_R(16, HOP_SHIFTED, true);
+    else if (gram) BCG_LAUNCH4B_R(8, HOP_SHIFTED, true);
     else if (mode == HOP_PLAIN) BCG_LAUNCH4B_R(M, HOP_PLAIN, false);
     else BCG_LAUNCH4B_R(M, HOP_SHIFTED, false);
 #undef BCG_LAUNCH4B_R
-#undef BCG_LAUNCH4B
-    return grid;
-  }
-  if (mode == HOP_RESID || fact) return -1;  // the fused residual form and the factored pair exist in the bundle sweep only
-  if (pl.column) {
-    if (hw.sync) (void)hipMemsetAsync(hw.sync, 0, sizeof(unsigned) * 8 * hw.sync_stride, s);
-    const size_t lds_u = sizeof(double2) * 2 * ((SPB + 1) * 36 + 3 * SPB * 9);
-    const size_t lds = lds_u > lds_g ? lds_u : lds_g;
-#define BCG_LAUNCH4C(MM, MD, GR, CL, RG)                                                                                \
-  do {                                                                                                                 \
-    allow_lds(k_hop4c<MM, MD, GR, CL, RG>, lds);                                                                       \
-    hipLaunchKernelGGL((k_hop4c<MM, MD, GR, CL, RG>), dim3(grid), dim3(256), lds, s, lat, U, Ughost, in, ghost, out, p, \
-                       c0, partials, hw, win);                                                                         \
+  } else if (pl.form == HOP_FORM_COLUMN) {
+#define BCG_LAUNCH4C_R(MM, MD, GR)                                                                   \
+  do {                                                                                               \
+    if (ring) BCG_LAUNCH((k_hop4c<MM, MD, GR, 0, true>), hw, win);                                   \
+    else if (pl.capped_interior) BCG_LAUNCH((k_hop4c_interior<MM, MD, GR>), hw, win);                \
+    else if (cls == 1) BCG_LAUNCH((k_hop4c<MM, MD, GR, 1, false>), hw, win);                         \
+    else if (cls == 2) BCG_LAUNCH((k_hop4c<MM, MD, GR, 2, false>), hw, win);                         \
+    else BCG_LAUNCH((k_hop4c<MM, MD, GR, 0, false>), hw, win);                                       \
   } while (0)
-#define BCG_LAUNCH4C_R(MM, MD, GR)                          \
-  do {                                                      \
-    if (win.ring > 0) BCG_LAUNCH4C(MM, MD, GR, 0, true);    \
-    else if (cls == 1 && (GR || MM == 8)) { /* interior variants over 256 VGPRs: register-capped entry point */ \
-      allow_lds(k_hop4c_interior<MM, MD, GR>, lds);         \
-      hipLaunchKernelGGL((k_hop4c_interior<MM, MD, GR>), dim3(grid), dim3(256), lds, s, lat, U, Ughost, in, ghost, out, p, \
-                         c0, partials, hw, win);            \
-    } else if (cls == 1) BCG_LAUNCH4C(MM, MD, GR, 1, false); \
-    else if (cls == 2) BCG_LAUNCH4C(MM, MD, GR, 2, false);  \
-    else BCG_LAUNCH4C(MM, MD, GR, 0, false);                \
-  } while (0)
-    if (gram && M == 16 && mode == HOP_SHIFTED) BCG_LAUNCH4C_R(16, HOP_SHIFTED, true);
-    else if (gram && M == 8 && mode == HOP_SHIFTED) BCG_LAUNCH4C_R(8, HOP_SHIFTED, true);
+    if (gram && M == 16) BCG_LAUNCH4C_R(16, HOP_SHIFTED, true);
+    else if (gram) BCG_LAUNCH4C_R(8, HOP_SHIFTED, true);
     else if (mode == HOP_PLAIN) BCG_LAUNCH4C_R(M, HOP_PLAIN, false);
     else BCG_LAUNCH4C_R(M, HOP_SHIFTED, false);
 #undef BCG_LAUNCH4C_R
-#undef BCG_LAUNCH4C
-    return grid;
-  }
-  // link images: three for the fused-Gram variant (x3 carry reads the previous one), two otherwise
-  const size_t lds_u = sizeof(double2) * ((gram && M == 16 && mode == HOP_SHIFTED) ? 3 : 2) * ((SPB + 1) * 36 + 3 * SPB * 9);
-  const size_t lds = lds_u > lds_g ? lds_u : lds_g;
-  // the streaming (non-temporal) form is the only one instantiated
-#define BCG_LAUNCH4(MM, MD, GR, CL, RG)                                                                                   \
-  do {                                                                                                                   \
-    allow_lds(k_hop4<MM, MD, GR, true, CL, RG>, lds);                                                                    \
-    hipLaunchKernelGGL((k_hop4<MM, MD, GR, true, CL, RG>), dim3(grid), dim3(256), lds, s, lat, U, Ughost, in, ghost, out, \
-                       p, c0, partials, ntiles, hw, win);                                                                \
+  } else {
+    // the streaming (non-temporal) form is the only one instantiated
+#define BCG_LAUNCH4_CLS(MM, MD, GR)                                                                  \
+  do {                                                                                               \
+    if (ring) BCG_LAUNCH((k_hop4<MM, MD, GR, true, 0, true>), ntiles, hw, win);                      \
+    else if (cls == 1) BCG_LAUNCH((k_hop4<MM, MD, GR, true, 1, false>), ntiles, hw, win);            \
+    else if (cls == 2) BCG_LAUNCH((k_hop4<MM, MD, GR, true, 2, false>), ntiles, hw, win);            \
+    else BCG_LAUNCH((k_hop4<MM, MD, GR, true, 0, false>), ntiles, hw, win);                          \
   } while (0)
-#define BCG_LAUNCH4_CLS(MM, MD, GR)                          \
-  do {                                                       \
-    if (win.ring > 0) BCG_LAUNCH4(MM, MD, GR, 0, true);      \
-    else if (cls_t == 1) BCG_LAUNCH4(MM, MD, GR, 1, false);  \
-    else if (cls_t == 2) BCG_LAUNCH4(MM, MD, GR, 2, false);  \
-    else BCG_LAUNCH4(MM, MD, GR, 0, false);                  \
-  } while (0)
-  if (gram && M == 16 && mode == HOP_SHIFTED) BCG_LAUNCH4_CLS(16, HOP_SHIFTED, true);
-  else if (mode == HOP_PLAIN) BCG_LAUNCH4_CLS(M, HOP_PLAIN, false);
-  else BCG_LAUNCH4_CLS(M, HOP_SHIFTED, false);
+    if (gram) BCG_LAUNCH4_CLS(16, HOP_SHIFTED, true);
+    else if (mode == HOP_PLAIN) BCG_LAUNCH4_CLS(M, HOP_PLAIN, false);
+    else BCG_LAUNCH4_CLS(M, HOP_SHIFTED, false);
 #undef BCG_LAUNCH4_CLS
-#undef BCG_LAUNCH4
-  return grid;
-}
-
-int hop_kernel_form(int m, const LatticeDev& lat, int max_blocks, const HopTuning& tune, int tile_class, const HopWindow& win) {
-  if (!hop_can_split_tiles(m, lat)) return 0;
-  const int mb = tune.blocks > 0 ? tune.blocks : max_blocks;
-  const HopPlan pl = plan_hop4(m, lat, mb, tune, tile_class, win);
-  return !pl.valid ? -1 : (pl.column ? 2 : 1);
-}
-
-bool hop_folds_gram(int m, const LatticeDev& lat, int max_blocks, const HopTuning& tune, const HopWindow& win) {
-  if (!hop_can_split_tiles(m, lat) || (m != 16 && m != 8)) return false;
-  const int mb = tune.blocks > 0 ? tune.blocks : max_blocks;
-  const HopPlan pl = plan_hop4(m, lat, mb, tune, 0, win);
-  return pl.valid && pl.column;
-}
-
-bool hop_uses_bundle(int m, const LatticeDev& lat, int max_blocks, const HopTuning& tune, int tile_class, const HopWindow& win,
-                     bool plain) {
-  if (!hop_can_split_tiles(m, lat)) return false;
-  const int mb = tune.blocks > 0 ? tune.blocks : max_blocks;
-  return bundle_ok(m, lat, tune, plan_hop4(m, lat, mb, tune, tile_class, win), tile_class, plain);
-}
-
-int launch_hop_fast(hipStream_t s, int m, const LatticeDev& lat, const double2* U, const double2* Ughost,
-                    const double2* in, const double2* ghost, double2* out, HopMode mode, const double2* p, double c0,
-                    double2* partials, bool gram, int max_blocks, const HopTuning& tune, int tile_class,
-                    const HopWindow& win) {
-  const int spb = 4 * (64 / m);
-  // specialised 4-D kernel: tile = spb consecutive x0 sites of one row, 32-bit site arithmetic
-  if (hop_can_split_tiles(m, lat)) {
-    const int mb = tune.blocks > 0 ? tune.blocks : max_blocks;
-    if (m == 8) return launch_hop4<8>(s, lat, U, Ughost, in, ghost, out, mode, p, c0, partials, gram, mb, tune, tile_class, win);
-    if (m == 16) return launch_hop4<16>(s, lat, U, Ughost, in, ghost, out, mode, p, c0, partials, gram, mb, tune, tile_class, win);
-    return launch_hop4<32>(s, lat, U, Ughost, in, ghost, out, mode, p, c0, partials, gram, mb, tune, tile_class, win);
   }
-  (void)spb;
-  return -1;  // no specialised form for this lattice: the caller runs k_hop_generic
+#undef BCG_LAUNCH
+}
+
+int hop_launch(hipStream_t s, const HopLaunchPlan& pl, const double2* U, const double2* Ughost, const double2* in,
+               const double2* ghost, double2* out, const double2* p, double c0, double2* partials) {
+  assert(pl.form != HOP_FORM_NONE && "hop_launch: a declined plan (the caller runs a generic kernel instead)");
+  if (pl.grid == 0) return 0;  // an empty tile list
+  HopWalk hw{pl.p0, pl.p1, pl.p2, pl.xcd_split, pl.sync, pl.sync_window, pl.sync_stride, pl.sync_limit, pl.tile_list, pl.list_n,
+             pl.fold, pl.super};
+  if (hw.sync) (void)hipMemsetAsync(hw.sync, 0, sizeof(unsigned) * 8 * hw.sync_stride, s);
+  if (pl.req.m == 8) launch_hop4<8>(s, pl, hw, U, Ughost, in, ghost, out, p, c0, partials);
+  else if (pl.req.m == 16) launch_hop4<16>(s, pl, hw, U, Ughost, in, ghost, out, p, c0, partials);
+  else launch_hop4<32>(s, pl, hw, U, Ughost, in, ghost, out, p, c0, partials);
+  return pl.grid;
 }
 
 }  // namespace bcg

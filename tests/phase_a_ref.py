@@ -22,7 +22,7 @@ RTYPE = np.longdouble if EXTENDED else np.float64
 PRECISION = f"{np.dtype(CTYPE).name} ({np.finfo(RTYPE).nmant} mantissa bits)"
 
 # The launch geometries of tests/test_phase_a_operator.py: name -> (dims, BCG_HOP_PATCH or None, BCG_HOP_BLOCKS or None).
-# Legal for the bundle sweep at m = 16 by plan_hop4 / bundle_ok (kernels_stencil.hip), tiles of 16 x0 sites, re-derived row by row:
+# Legal for the bundle sweep at m = 16 by plan_hop4 / bundle_ok (hop_plan.cpp), tiles of 16 x0 sites, re-derived row by row:
 # whole patches (p0 | L0, 16 | p0, p1 | L1, p2 | L2, p1 and p2 even), tiles = V / 16 a multiple of 8 and >= blocks, patches
 # (L0/p0)(L1/p1)(L2/p2) a multiple of 8, blocks / 8 = (p0/16) p1 p2 [column form] = (p0/4)(p1/2)(p2/2) [bundles]:
 #   16x4x8xL3    16,2,2 / 32   tiles 32 L3    patches 1*2*4 = 8     32/8 = 4 = 1*2*2 = 4*1*1

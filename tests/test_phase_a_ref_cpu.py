@@ -56,7 +56,7 @@ def test_reference_shift_is_additive_and_unfactored():
 
 
 def test_every_geometry_is_legal_for_the_bundle_sweep():
-    """plan_hop4 / bundle_ok (kernels_stencil.hip) at m = 16, restated: the table in phase_a_ref.py row by row."""
+    """plan_hop4 / bundle_ok (hop_plan.cpp) at m = 16, restated: the table in phase_a_ref.py row by row."""
     for name, (dims, patch, blocks) in ref.ALL_SHAPES.items():
         p0, p1, p2 = (int(v) for v in patch.split(",")) if patch else (16, 8, 8)
         nb = int(blocks) if blocks else 512
