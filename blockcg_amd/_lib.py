@@ -131,6 +131,13 @@ SIGNATURES = {
     "bcg_basis_dot": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_void_p, c_dbl_p]),
     "bcg_basis_axpy": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, c_dbl_p, ctypes.c_double]),
     "bcg_field_copy_columns": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),
+    "bcg_basis_rotate": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, c_dbl_p]),
+    "bcg_spectral_bound": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_uint64, c_dbl_p]),
+    "bcg_lowest_modes": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.POINTER(ctypes.c_void_p),
+                                        ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_double, ctypes.c_double, ctypes.c_int, c_dbl_p, c_dbl_p, c_int_p,
+                                        ctypes.POINTER(ctypes.c_int64)]),
 }
 
 _lib = None

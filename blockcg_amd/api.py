@@ -570,6 +570,54 @@ def SBCGrQ_deflated(X, B, D, sigma, V, evals, eps=1.e-15, eps_shifts=1.e-15, max
     return r
 
 
+BASIS_ROTATE_MAX_COLUMNS = 64
+
+
+def basis_rotate(V, Q):
+    """V <- V Q in place (bcg_basis_rotate): V a list of fields of widths 1..32 whose widths sum to K <= 64, Q a (K, K) array
+    that need not be unitary; column j of the result is sum_i V_i Q[i, j].  One launch takes all K columns and needs no second
+    copy of the basis.  Purely local."""
+    Vh, nv, K = _basis_handles(V)
+    Q = np.asarray(Q, dtype=np.complex128)
+    if Q.shape != (K, K):
+        raise ValueError(f"expected a {K}x{K} matrix")
+    Qt = np.ascontiguousarray(Q.T)  # column-major buffer
+    V[0].ctx.check(V[0].ctx.lib.bcg_basis_rotate(Vh, nv, _dp(Qt)))
+    return V
+
+
+def spectral_bound(D, steps=10, seed=1, parity=None):
+    """An upper bound on the largest eigenvalue of D.op (parity None) or of its block of one parity (0 / 1): theta_max + beta
+    of a `steps`-step Lanczos run from Gaussian noise (bcg_spectral_bound)."""
+    out = ctypes.c_double()
+    D.ctx.check(D.ctx.lib.bcg_spectral_bound(D.ctx.h, D.h, D.mass, -1 if parity is None else int(parity), int(steps), int(seed),
+                                             ctypes.byref(out)))
+    return out.value
+
+
+def lowest_modes(V, D, n_want, upper_bound, degree=16, tol=1e-10, max_iterations=100, locked=None):
+    """Chebyshev-filtered subspace iteration for the lowest eigenpairs of D.op (bcg_lowest_modes).  V: the start block (a list
+    of fields, K <= 64 columns in all, filled by the caller), on return orthonormal Ritz vectors with ascending Ritz values;
+    locked: converged orthonormal vectors V is kept orthogonal to.  Converged when the residuals of the first n_want columns
+    are at most tol * upper_bound; reaching max_iterations is no error.  The top columns of the block the iteration carries
+    sit on the edge of the interval the filter damps and converge slowly or not at all, so the wanted columns need columns
+    beyond them; with n_want == K the call carries a guard block of min(16, 64 - K) columns of its own.  Returns a dict: evals and resid (K each), iterations
+    (filter applications), applications (calls of the block operator)."""
+    Vh, nv, K = _basis_handles(V)
+    if locked:
+        Lh, nl, _ = _basis_handles(locked)
+    else:
+        Lh, nl = None, 0
+    evals = np.zeros(K)
+    resid = np.zeros(K)
+    it = ctypes.c_int()
+    apps = ctypes.c_int64()
+    D.ctx.check(D.ctx.lib.bcg_lowest_modes(D.ctx.h, D.h, D.mass, Vh, nv, Lh, nl, int(n_want), int(degree), float(upper_bound),
+                                           float(tol), int(max_iterations), _dp(evals), _dp(resid), ctypes.byref(it),
+                                           ctypes.byref(apps)))
+    return dict(evals=evals, resid=resid, iterations=it.value, applications=apps.value)
+
+
 def _trace_buffers(trace_limit, S, m):
     if trace_limit <= 0:
         return None, None, None

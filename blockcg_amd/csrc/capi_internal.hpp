@@ -6,6 +6,8 @@
 //   capi_sources.hip    noise fields, point / wall sources, the slice-resolved inner product
 //   capi_shift.hip      the covariant nearest-neighbour sum with free coefficients, covariant smearing
 //   capi_basis.hip      products between fields of unequal width (V^dagger b, y <- beta y + V C), the column copy
+//   capi_rotate.hip     V <- V Q in place for a whole basis of at most 64 columns
+//   capi_lowmodes.hip   the low-mode eigensolver: Lanczos bound, Chebyshev-filtered subspace iteration (host composition)
 // Host code only; every loop over lattice sites is a HIP kernel (kernels_generic.hip, kernels_mfma.hip, kernels_stencil.hip).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -96,6 +96,9 @@ struct bcg_context {
   double* pin_basis = nullptr;           // pinned host copy
   size_t basis_entries = 0;              // complex entries either holds; grown on demand
   hipEvent_t basis_uploaded = nullptr;   // the last upload from pin_basis has left the host buffer
+  double2* dev_rotate = nullptr;         // K x K matrix of bcg_basis_rotate, K <= 64 (capi_rotate.hip); allocated on first use
+  double* pin_rotate = nullptr;          // pinned host copy
+  hipEvent_t rotate_uploaded = nullptr;  // the last upload from pin_rotate has left the host buffer
   double2* staging = nullptr;            // layout-conversion staging of bcg_field_download_sites
   size_t staging_bytes = 0;
   // host <-> device pipeline of bcg_field_upload / bcg_field_download: two chunks in flight, each with its own stream,

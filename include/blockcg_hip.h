@@ -428,6 +428,58 @@ int bcg_basis_dot(const bcg_field* const* V, int nv, const bcg_field* b, double*
 int bcg_basis_axpy(bcg_field* y, const bcg_field* const* V, int nv, const double* C, double beta);
 int bcg_field_copy_columns(bcg_field* dst, int dst_first, const bcg_field* src, int src_first, int n);
 
+/* ---- low modes: the in-place basis rotation and the eigensolver built on it (extensions) ----------
+ * bcg_basis_rotate: V <- V Q in place.  V as in bcg_basis_dot (one context, parity and site count, widths 1 .. 32, no field
+ * twice), K the sum of the widths, at most BCG_BASIS_ROTATE_MAX_COLUMNS; Q is K x K, column-major, interleaved (re, im),
+ * and need not be unitary.  Column j of the result is sum_i V_i Q(i, j).  One launch takes all K columns: a 16-row tile of
+ * every column is read, the outputs formed from that copy and stored over their inputs -- no workspace, no second copy of
+ * the basis.  Every width in {16, 32} takes the MFMA form, every other width list and bcg_force_generic the generic one.
+ * Purely local (no communication call), no atomics: the same bits on every call.  A permutation matrix moves columns bit
+ * for bit.  Profile keys "basis_rotate" (96 K bytes per site, 8 K^2 flops per row), "basis_rotate_mfma" /
+ * "basis_rotate_generic" (launch counts).  The uploaded Q lives in a buffer of the context's own (64 x 64 entries, device
+ * and pinned host), allocated on first use, freed by bcg_context_destroy.
+ * BCG_ERR_INVALID: a NULL pointer, nv < 1, a field listed twice, mixed contexts, parities or site counts, a non-finite Q.
+ * BCG_ERR_UNSUPPORTED: K > 64.  Either is returned before the first launch and leaves V exactly as it was.
+ *
+ * bcg_spectral_bound: an upper bound on the largest eigenvalue of dirac_op::op (full fields: parity -1; the block of one
+ * parity: 0 / 1) from `steps` (2 .. 64) Lanczos steps on one column started from bcg_field_fill_noise(GAUSSIAN, seed):
+ * theta_max(T_k) + beta_k, the safeguarded bound of Zhou and Saad.  Allocates and frees three fields of width 1.
+ *
+ * bcg_lowest_modes: Chebyshev-filtered subspace iteration for the lowest eigenpairs of dirac_op::op.
+ *   V           in: the start block (the caller fills it, e.g. with noise); out: orthonormal Ritz vectors, Ritz values
+ *               ascending over the K columns.  K <= 64; wider bases are built 64 at a time with `locked`.
+ *   locked      NULL / 0, or orthonormal, already converged vectors of any total width: V is kept orthogonal to them.
+ *   n_want      the first n_want columns decide convergence: max_i resid_i <= tol * upper_bound.  The filter damps
+ *               everything above the largest Ritz value of the block it carries, so the top columns of that block converge
+ *               slowly or not at all: the wanted columns need columns beyond them.  Half as many spare columns as wanted
+ *               ones is a good start.  With n_want == K the caller brings none, and the call carries a guard block of its
+ *               own: one more field of min(16, 64 - K) columns of noise (a fixed seed, a function of the global site),
+ *               allocated for the call, filtered, orthonormalised and rotated with V and dropped at the end; V gets the
+ *               lowest K of the K + guard Ritz vectors.  K == 64 leaves no room for one.
+ *   degree      of the Chebyshev polynomial per outer iteration (>= 2); upper_bound: of the spectrum (bcg_spectral_bound).
+ *   evals_out, resid_out   K each: Ritz values and ||A v_i - theta_i v_i|| of the vectors left in V.
+ *   iterations_out         filter applications made; applications_out: calls of the block operator, one per field and
+ *                          application: nf (2 (iterations + 1) + degree iterations), nf = nv, or nv + 1 with the guard
+ *                          block.  Either may be NULL.
+ * An outer iteration: project out the locked vectors, G = V^dagger V, Cholesky, V <- V R^-1; the same again with
+ * H = V^dagger A V beside it and V <- V R^-1 Z from the reduced eigenproblem (two rotations per iteration in all); residuals
+ * from A v - theta v itself; then, unless converged, the filter that damps [theta_K, upper_bound].  Reaching
+ * max_iterations is not an error: BCG_OK, and resid_out tells.  The call allocates and frees three work fields of the
+ * widest width.  Every branch is taken on all-reduced data: all ranks of a divided lattice return the same status.
+ * BCG_ERR_INVALID: a NULL pointer, nv < 1, a field twice, a locked field that is also in V, mixed contexts, parities or site
+ * counts, n_want outside 1 .. K, degree < 2, max_iterations < 0, a tol or upper_bound that is not finite and positive.
+ * BCG_ERR_UNSUPPORTED: K > 64.  Both before anything is launched.  BCG_ERR_NUMERIC: V^dagger V not positive definite (the
+ * block lost rank), a Ritz value at or above upper_bound, or Ritz values that do not spread; V then holds the
+ * block as the failed step found it (same span, not orthonormal), evals_out / resid_out the last completed Ritz step. */
+#define BCG_BASIS_ROTATE_MAX_COLUMNS 64
+int bcg_basis_rotate(bcg_field* const* V, int nv, const double* Q);
+int bcg_spectral_bound(bcg_context* ctx, const bcg_gauge* g, double mass, int parity, int steps, uint64_t seed,
+                       double* bound_out);
+int bcg_lowest_modes(bcg_context* ctx, const bcg_gauge* g, double mass, bcg_field* const* V, int nv,
+                     const bcg_field* const* locked, int nlocked, int n_want, int degree, double upper_bound, double tol,
+                     int max_iterations, double* evals_out, double* resid_out, int* iterations_out,
+                     int64_t* applications_out);
+
 #ifdef __cplusplus
 }
 #endif
