@@ -526,6 +526,31 @@ def basis_dot(V, b):
     return np.ascontiguousarray(out.T)
 
 
+def basis_slice_dot(V, b, dir, momenta=None):
+    """V^dagger b resolved by slice: [L_dir global, K, m] with entry (t, i, j) = sum over the sites of slice x_dir = t and the
+    colours of conj(V_i) * b_j, V as in basis_dot; its sum over t is basis_dot(V, b).  momenta: a list of integer momenta (ndim
+    or 4 entries each, the entry along dir 0) gives [P, L_dir, K, m] with the summand weighted by
+    exp(-2 pi i sum_mu n_mu x_mu / L_mu) of the GLOBAL coordinates, as in block_fermion_field.slice_gram.  Summed over ranks and
+    identical on every rank (include/blockcg_hip.h, bcg_basis_slice_dot).  b may be one of V."""
+    Vh, nv, K = _basis_handles(V)
+    if not 0 <= int(dir) < b.ctx.ndim:
+        raise BlockCGError(1, "basis_slice_dot: direction outside the lattice")
+    m, L = b.N_rhs, b.ctx.dims[int(dir)]
+    if momenta is None:
+        out = np.empty((L, m, K), dtype=np.complex128)
+        b.ctx.check(b.ctx.lib.bcg_basis_slice_dot(Vh, nv, b.h, int(dir), 0, None, _dp(out)))
+        return np.ascontiguousarray(out.transpose(0, 2, 1))
+    mom = [list(p) for p in momenta]
+    if not mom or any(len(p) > 4 for p in mom):
+        raise BlockCGError(1, "basis_slice_dot: momenta is a non-empty list of up to 4 integers each")
+    ns = np.zeros((len(mom), 4), dtype=np.intc)
+    for k, p in enumerate(mom):
+        ns[k, :len(p)] = p
+    out = np.empty((len(mom), L, m, K), dtype=np.complex128)
+    b.ctx.check(b.ctx.lib.bcg_basis_slice_dot(Vh, nv, b.h, int(dir), len(mom), ns.ctypes.data_as(_lib.c_int_p), _dp(out)))
+    return np.ascontiguousarray(out.transpose(0, 1, 3, 2))
+
+
 def basis_axpy(y, V, C, beta=1.0):
     """y <- beta y + V C with C a (K, m) array (bcg_basis_axpy).  beta exactly 0 does not read y.  y is none of V."""
     Vh, nv, K = _basis_handles(V)

@@ -1,12 +1,20 @@
 // include/blockcg_hip.h: products between fields of unequal width -- C = V^dagger b (bcg_basis_dot) and y <- beta y + V C
 // (bcg_basis_axpy) for a list V of fields whose widths sum to K != m -- and the column copy between widths
 // (bcg_field_copy_columns).  Kernels: kernels_basis.hip.  The host walks V in groups of consecutive fields (one launch per
-// group, kernels_basis.hpp); the K x m matrix lives in c->dev_basis / c->pin_basis, which grow on demand.
+// group, kernels_basis.hpp); the K x m matrix lives in c->dev_basis / c->pin_basis, which grow on demand.  And the dot
+// resolved by slice and momentum (bcg_basis_slice_dot; kernels and plan: kernels_basis_slice.hip / .hpp), whose
+// P x L_dir x K x m result is assembled in the same buffer.
 #include "capi_internal.hpp"
 #include "kernels_basis.hpp"
+#include "kernels_basis_slice.hpp"
 
 namespace bcg_impl {
 namespace {
+
+// bcg_basis_slice_dot: the phase tables and the block partials take the first half of c->partials (ensure_scratch), as in
+// bcg_field_slice_gram; the whole result, P x L_dir x K x m, is at most 2^26 entries (1 GiB) of c->dev_basis
+constexpr int64_t kBasisSliceHalf = static_cast<int64_t>(kMaxGramBlocks) * 32 * 32 / 2;
+constexpr int64_t kBasisSliceEntries = static_cast<int64_t>(1) << 26;
 
 struct BasisGroup {
   bool mfma;
@@ -140,6 +148,112 @@ int bcg_basis_dot(const bcg_field* const* V, int nv, const bcg_field* b, double*
       bcg::launch_basis_fold(c->stream, g.K, m, nblocks, c->partials, c->dev_basis, static_cast<int>(K), g.off);
     }
     BCG_TRY(check_launch(c, "basis_fold"));
+  }
+  if (c->distributed) {
+    ProfScope ps(c, "allreduce");
+    if (c->comm.allreduce_sum(c->comm.user, c->dev_basis, 2 * entries) != 0) BCG_FAIL(c, BCG_ERR_COMM, "allreduce_sum callback failed");
+  }
+  HIP_TRY(c, hipEventSynchronize(c->basis_uploaded));  // an upload of bcg_basis_axpy may still read pin_basis
+  HIP_TRY(c, hipMemcpyAsync(c->pin_basis, c->dev_basis, entries * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
+  BCG_TRY(stream_sync(c));
+  std::memcpy(out, c->pin_basis, entries * sizeof(double2));
+  return BCG_OK;
+}
+
+int bcg_basis_slice_dot(const bcg_field* const* V, int nv, const bcg_field* b, int dir, int n_mom, const int* momenta, double* out) {
+  DeviceScope on_device(b ? b->ctx : nullptr);
+  const int64_t K = basis_columns(V, nv, b);
+  if (K < 0 || !out) return BCG_ERR_INVALID;
+  bcg_context* c = b->ctx;
+  if (dir < 0 || dir >= c->ndim) BCG_FAIL(c, BCG_ERR_INVALID, "bcg_basis_slice_dot: direction outside the lattice");
+  if (n_mom < 0 || (n_mom > 0 && !momenta)) BCG_FAIL(c, BCG_ERR_INVALID, "bcg_basis_slice_dot: n_mom momenta are needed");
+  for (int p = 0; p < n_mom; ++p)
+    for (int mu = 0; mu < 4; ++mu)
+      if ((mu == dir || mu >= c->ndim) && momenta[4 * p + mu] != 0)
+        BCG_FAIL(c, BCG_ERR_INVALID, "bcg_basis_slice_dot: momentum component along dir or beyond the lattice's dimensions");
+  if (c->distributed && (!c->have_comm || !c->comm.allreduce_sum))
+    BCG_FAIL(c, BCG_ERR_COMM, "lattice is split over ranks but no bcg_comm was set");
+  const int m = b->m;
+  const int P = n_mom > 0 ? n_mom : 1;
+  const int Lg = c->gdims[dir], Ll = c->lat.L[dir];
+  const int64_t per = static_cast<int64_t>(Lg) * K * m;  // entries of one momentum
+  if (per > kBasisSliceEntries / P) BCG_FAIL(c, BCG_ERR_UNSUPPORTED, "bcg_basis_slice_dot: more than 2^26 entries; split the momenta");
+  const size_t entries = static_cast<size_t>(per) * P;
+  std::vector<int> widths(nv);
+  for (int k = 0; k < nv; ++k) widths[k] = V[k]->m;
+  bcg::BasisSlicePlan plan;
+  if (!bcg::basis_slice_plan(widths.data(), nv, m, !c->force_generic, c->lat, b->parity, dir, n_mom, kBasisSliceHalf, &plan))
+    BCG_FAIL(c, BCG_ERR_UNSUPPORTED, "bcg_basis_slice_dot: one launch does not fit the context's scratch");
+  int rc = ensure_scratch(c);
+  if (rc == BCG_OK) rc = ensure_basis(c, entries);
+  rc = agree_on_allocation(c, rc, "bcg_basis_slice_dot", "the P x L_dir x K x m result");
+  if (rc != BCG_OK) {
+    if (c->distributed) release_basis(c);  // every rank starts the next call from the same state
+    return rc;
+  }
+  // c->partials, first half: [phase tables][block partials]; the result is assembled in c->dev_basis
+  double2* const tab_dev = c->partials;
+  double2* const partials = c->partials + (n_mom > 0 ? bcg::basis_slice_table_entries(plan) : 0);
+  // the tables of every momentum (a launch's unused momenta: ones), from global coordinates: nothing depends on the grid
+  std::vector<double2> tabs;
+  const int64_t per_tab = static_cast<int64_t>(3) * plan.ltab;
+  if (n_mom > 0) {
+    tabs.assign(static_cast<size_t>(per_tab) * (P + plan.pc_max()), make_double2(1.0, 0.0));
+    for (int p = 0; p < P; ++p)
+      for (int s = 0; s < 3; ++s) {
+        const int mu = plan.mu[s];
+        for (int x = 0; x < c->lat.L[mu]; ++x)
+          tabs[p * per_tab + static_cast<int64_t>(s) * plan.ltab + x] = momentum_phase(momenta[4 * p + mu], c->lat.origin[mu] + x, c->gdims[mu]);
+      }
+  }
+  if (c->lat.split[dir])  // the slices of the other ranks: zeros from this one
+    HIP_TRY(c, hipMemsetAsync(c->dev_basis, 0, entries * sizeof(double2), c->stream));
+  // the 16-column blocks of the MFMA fields of V, in order: an MFMA group is a run of them
+  std::vector<const double2*> block_p;
+  std::vector<int> block_ld;
+  for (int k = 0; k < nv; ++k)
+    if (!c->force_generic && (m == 16 || m == 32) && bcg::basis_mfma_width(V[k]->m))
+      for (int c0 = 0; c0 < V[k]->m; c0 += 16) {
+        block_p.push_back(V[k]->d + c0);
+        block_ld.push_back(V[k]->m);
+      }
+  for (const bcg::BasisSliceGroup& g : plan.groups) {
+    const int pc_g = plan.pc_of(g);
+    bcg::BasisBlocks blocks{};
+    bcg::BasisFields fields{};
+    if (g.mfma) {
+      for (int q = 0; q < g.count; ++q) {
+        blocks.p[q] = block_p[g.first + q];
+        blocks.ld[q] = block_ld[g.first + q];
+      }
+    } else {
+      BasisGroup fg{false, g.first, g.count, g.K, g.off};
+      fields = group_fields(V, fg);
+    }
+    for (int p0 = 0; p0 < P; p0 += pc_g) {
+      const int n = std::min(pc_g, P - p0);
+      const int pc = bcg::basis_slice_launch_pc(n);
+      if (n_mom > 0)
+        HIP_TRY(c, hipMemcpyAsync(tab_dev, tabs.data() + p0 * per_tab, static_cast<size_t>(pc * per_tab) * sizeof(double2),
+                                  hipMemcpyHostToDevice, c->stream));
+      {
+        ProfScope ps(c, "basis_slice_dot", static_cast<double>(b->sites) * 48.0 * (g.K + m), static_cast<double>(rows_of(b)) * 8.0 * g.K * m * pc);
+        ProfScope form(c, g.mfma ? "basis_slice_form_mfma" : "basis_slice_form_generic");
+        if (g.mfma)
+          bcg::launch_basis_slice_dot_mfma(c->stream, m, g.count, c->lat, b->parity, dir, plan, pc, blocks, b->d, n_mom > 0 ? tab_dev : nullptr,
+                                           partials);
+        else
+          bcg::launch_basis_slice_dot_generic(c->stream, m, c->lat, b->parity, dir, plan, pc, fields, b->d, n_mom > 0 ? tab_dev : nullptr,
+                                              partials);
+      }
+      BCG_TRY(check_launch(c, "basis_slice_dot"));
+      {
+        ProfScope ps(c, "basis_slice_fold");
+        bcg::launch_basis_slice_fold(c->stream, g.K, m, pc, n, Ll, Lg, plan.nbps, c->lat.origin[dir], static_cast<int>(K), g.off, p0, partials,
+                                     c->dev_basis);
+      }
+      BCG_TRY(check_launch(c, "basis_slice_fold"));
+    }
   }
   if (c->distributed) {
     ProfScope ps(c, "allreduce");

@@ -5,7 +5,7 @@
 //   capi_force.hip      the fermion force of multi-shift solutions (bcg_force_accumulate), gauge-field download / zero
 //   capi_sources.hip    noise fields, point / wall sources, the slice-resolved inner product
 //   capi_shift.hip      the covariant nearest-neighbour sum with free coefficients, covariant smearing
-//   capi_basis.hip      products between fields of unequal width (V^dagger b, y <- beta y + V C), the column copy
+//   capi_basis.hip      products between fields of unequal width (V^dagger b, y <- beta y + V C, V^dagger b by slice), the column copy
 //   capi_rotate.hip     V <- V Q in place for a whole basis of at most 64 columns
 //   capi_lowmodes.hip   the low-mode eigensolver: Lanczos bound, Chebyshev-filtered subspace iteration (host composition)
 // Host code only; every loop over lattice sites is a HIP kernel (kernels_generic.hip, kernels_mfma.hip, kernels_stencil.hip).
@@ -160,6 +160,15 @@ int axpby(bcg_context* c, bcg_field* y, double a, const bcg_field* x, double b, 
 int create_like(bcg_context* c, const bcg_field* like, bcg_field** out);  // a new field of the width, parity and site count of `like`
 // divided lattice: all-reduce whether any rank failed its allocations (alloc_rc != BCG_OK) before the first exchange
 int agree_on_allocation(bcg_context* c, int alloc_rc, const char* who, const char* what);
+// exp(-2 pi i k / L) for k = (n x) mod L, reduced exactly in integers; n any integer, x a global coordinate.  The one source
+// of the momentum phase tables (bcg_field_slice_gram, bcg_basis_slice_dot)
+inline double2 momentum_phase(int n, int x, int L) {
+  const int64_t nn = ((static_cast<int64_t>(n) % L) + L) % L;
+  const int64_t k = (nn * x) % L;
+  if (k == 0) return make_double2(1.0, 0.0);
+  const double th = 2.0 * M_PI * static_cast<double>(k) / static_cast<double>(L);
+  return make_double2(std::cos(th), -std::sin(th));
+}
 
 // ---- capi_operator.hip -----------------------------------------------------------------------------
 int halo_plan(int ndim, const int* gdims, const int* grid, const int* coords, size_t site_bytes, int* peer_s, int* peer_r,

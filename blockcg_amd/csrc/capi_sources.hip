@@ -19,15 +19,6 @@ bool colours_ok(const int* colour, int m) {
   return true;
 }
 
-// exp(-2 pi i k / L) for k = (n x) mod L, reduced exactly in integers; n any integer, x a global coordinate
-double2 momentum_phase(int n, int x, int L) {
-  const int64_t nn = ((static_cast<int64_t>(n) % L) + L) % L;
-  const int64_t k = (nn * x) % L;
-  if (k == 0) return make_double2(1.0, 0.0);
-  const double th = 2.0 * M_PI * static_cast<double>(k) / static_cast<double>(L);
-  return make_double2(std::cos(th), -std::sin(th));
-}
-
 }  // namespace
 }  // namespace bcg_impl
 

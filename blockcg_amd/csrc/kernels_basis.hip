@@ -10,12 +10,6 @@ namespace bcg {
 
 namespace {
 
-__device__ __forceinline__ void cfma_conj(double2& acc, double2 a, double2 b) {
-  acc.x = fma(a.x, b.x, acc.x);
-  acc.x = fma(a.y, b.y, acc.x);
-  acc.y = fma(a.x, b.y, acc.y);
-  acc.y = fma(-a.y, b.x, acc.y);
-}
 __device__ __forceinline__ void cfma(double2& acc, double2 a, double2 b) {
   acc.x = fma(a.x, b.x, acc.x);
   acc.x = fma(-a.y, b.y, acc.x);
@@ -89,21 +83,6 @@ __global__ void __launch_bounds__(256) k_basis_dot_mfma(int64_t rows, BasisBlock
       dst[j * KG + i] = make_double2(sr, si);
     }
   }
-}
-
-// the field that holds column i of a generic group: selects over the (few) fields, no indexed access to the argument
-__device__ __forceinline__ const double2* basis_column(const BasisFields& g, int i, int* w, int* o) {
-  const double2* p = g.v[0];
-  *w = g.w[0];
-  *o = 0;
-#pragma unroll
-  for (int k = 1; k < kBasisGenericFields; ++k)
-    if (k < g.nv && i >= g.off[k]) {
-      p = g.v[k];
-      *w = g.w[k];
-      *o = g.off[k];
-    }
-  return p;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -39,6 +39,33 @@ struct BasisFields {  // generic form: field k has w[k] columns, the group's col
 
 inline bool basis_mfma_width(int w) { return w == 16 || w == 32; }
 
+namespace {  // device helpers of the generic form, shared by kernels_basis.hip and kernels_basis_slice.hip
+
+// acc += conj(a) b
+__device__ __forceinline__ void cfma_conj(double2& acc, double2 a, double2 b) {
+  acc.x = fma(a.x, b.x, acc.x);
+  acc.x = fma(a.y, b.y, acc.x);
+  acc.y = fma(a.x, b.y, acc.y);
+  acc.y = fma(-a.y, b.x, acc.y);
+}
+
+// the field that holds column i of a generic group: selects over the (few) fields, no indexed access to the argument
+__device__ __forceinline__ const double2* basis_column(const BasisFields& g, int i, int* w, int* o) {
+  const double2* p = g.v[0];
+  *w = g.w[0];
+  *o = 0;
+#pragma unroll
+  for (int k = 1; k < kBasisGenericFields; ++k)
+    if (k < g.nv && i >= g.off[k]) {
+      p = g.v[k];
+      *w = g.w[k];
+      *o = g.off[k];
+    }
+  return p;
+}
+
+}  // namespace
+
 // Block partials of the group's K_g x m product: partials[block][j * K_g + i].  Returns the number of blocks.
 int launch_basis_dot_mfma(hipStream_t s, int m, int nblocks16, int64_t rows, const BasisBlocks& g, const double2* b, double2* partials);
 int launch_basis_dot_generic(hipStream_t s, int m, int64_t rows, const BasisFields& g, const double2* b, double2* partials);

@@ -4,60 +4,11 @@
 // kernel with the rows of a chunk staged in LDS.  Plain stores, no atomics; 64-bit wherever an element offset is formed.
 #include "kernels_slice_gram.hpp"
 #include "mfma_common.hpp"
+#include "slice_walk.hpp"
 
 namespace bcg {
 
 namespace {
-
-struct SGGeom {
-  int n_virtual;  // rows of one slice (half0: counting the skipped sites)
-  int run;        // rows per run
-  int inner;      // sites per run
-  int chunk;      // rows per block
-  int Leff;       // runs between those of consecutive o: L (half0: L0 / 2)
-  int nbps;       // blocks per slice
-  int half0;      // half field, dir = 0
-  int half;       // half field, dir > 0: slot 0 is the compact x0
-  int e0, e1;     // extents of slots 0 and 1 in the slice's site index c0 + e0 (c1 + e1 c2)
-  int par_off;    // half fields: field parity + parity of the local origin
-  int ltab;       // entries per phase table
-};
-
-struct SGRow {
-  int64_t row;  // row of the field
-  bool ok;      // it exists and the field holds it
-  int x[3];     // local coordinates of its site along the three slots (0 where !ok)
-};
-
-// virtual row v = o * run + e of slice t; live: v is inside the block's chunk
-template <bool COORDS>
-__device__ __forceinline__ SGRow sg_row(const SGGeom& g, int t, int teff, int o, int e, bool live) {
-  SGRow r;
-  r.ok = live;
-  r.row = (static_cast<int64_t>(o) * g.Leff + teff) * g.run + e;
-  r.x[0] = r.x[1] = r.x[2] = 0;
-  if (COORDS || g.half0) {
-    const int idx = live ? o * g.inner + e / 3 : 0;
-    const int q = idx / g.e0;
-    const int c0 = idx - q * g.e0;
-    const int c2 = q / g.e1;
-    const int c1 = q - c2 * g.e1;
-    if (g.half0) r.ok = live && ((c0 + c1 + c2 + g.par_off + t) & 1) == 0;
-    r.x[0] = g.half ? 2 * c0 + ((c1 + c2 + t + g.par_off) & 1) : c0;
-    r.x[1] = c1;
-    r.x[2] = c2;
-  }
-  return r;
-}
-
-__device__ __forceinline__ double2 cmul(double2 a, double2 b) {
-  return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-// w_p of a site: the three table entries multiplied in ascending direction
-__device__ __forceinline__ double2 sg_phase(const double2* __restrict__ tab, int ltab, int p, const int x[3]) {
-  const double2* tp = tab + static_cast<int64_t>(p) * 3 * ltab;
-  return cmul(cmul(tp[x[0]], tp[ltab + x[1]]), tp[2 * ltab + x[2]]);
-}
 
 __device__ __forceinline__ void cfma_conj(double2& acc, double2 a, double2 b) {
   acc.x = fma(a.x, b.x, acc.x);
@@ -259,20 +210,6 @@ void launch_generic(hipStream_t s, unsigned blocks, int m, const SGGeom& g, cons
   else hipLaunchKernelGGL((k_slice_gram_generic<PC, PHASE, false>), dim3(blocks), dim3(256), 0, s, m, g, a, b, tab, partials);
 }
 
-// rows of one slice, rows and sites per run
-void slice_rows(const LatticeDev& lat, int parity, int dir, int64_t* n_virtual, int64_t* run, int64_t* inner) {
-  const int L = lat.L[dir];
-  if (parity >= 0 && dir == 0) {
-    *inner = 1;
-    *run = 3;
-    *n_virtual = lat.V / L * 3;  // every (x1, x2, x3); half of them hold x0 = t
-  } else {
-    *inner = parity >= 0 ? lat.stride[dir] / 2 : lat.stride[dir];  // half: x0 is compact
-    *run = *inner * 3;
-    *n_virtual = lat.V / (lat.stride[dir] * L) * *run;
-  }
-}
-
 bool use_mfma(int m, bool mfma) { return mfma && (m == 16 || m == 32); }
 
 }  // namespace
@@ -316,21 +253,7 @@ bool slice_gram_plan(int m, bool mfma, const LatticeDev& lat, int parity, int di
 
 void launch_slice_gram(hipStream_t s, int m, bool mfma, const LatticeDev& lat, int parity, int dir, const SliceGramPlan& plan, int pc,
                        const double2* a, const double2* b, const double2* tab, double2* partials) {
-  int64_t n_virtual, run, inner;
-  slice_rows(lat, parity, dir, &n_virtual, &run, &inner);
-  SGGeom g{};
-  g.n_virtual = static_cast<int>(n_virtual);
-  g.run = static_cast<int>(run);
-  g.inner = static_cast<int>(inner);
-  g.chunk = plan.chunk;
-  g.nbps = plan.nbps;
-  g.half0 = parity >= 0 && dir == 0;
-  g.half = parity >= 0 && dir != 0;
-  g.Leff = g.half0 ? lat.L[0] / 2 : lat.L[dir];
-  g.e0 = g.half ? lat.L[0] / 2 : lat.L[plan.mu[0]];
-  g.e1 = lat.L[plan.mu[1]];
-  g.par_off = parity >= 0 ? parity + ((lat.origin[0] + lat.origin[1] + lat.origin[2] + lat.origin[3]) & 1) : 0;
-  g.ltab = plan.ltab;
+  const SGGeom g = slice_geom(lat, parity, dir, plan.chunk, plan.nbps, plan.ltab, plan.mu);
   const unsigned blocks = static_cast<unsigned>(plan.nbps) * static_cast<unsigned>(lat.L[dir]);
   if (use_mfma(m, mfma)) {
     if (m == 16) {

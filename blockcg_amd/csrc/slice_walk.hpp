@@ -1,0 +1,101 @@
+// The slice walk shared by the per-slice Gram kernels (kernels_slice_gram.hip) and the per-slice basis products
+// (kernels_basis_slice.hip): which rows of a field belong to slice t of a direction, in which order a block takes them, the
+// coordinates of a row's site and its momentum phase.  The walk itself is described in kernels_slice_gram.hpp.  Everything
+// lives in an anonymous namespace: each translation unit has its own copy, as with mfma_common.hpp.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "kernels.hpp"
+
+namespace bcg {
+
+namespace {
+
+struct SGGeom {
+  int n_virtual;  // rows of one slice (half0: counting the skipped sites)
+  int run;        // rows per run
+  int inner;      // sites per run
+  int chunk;      // rows per block
+  int Leff;       // runs between those of consecutive o: L (half0: L0 / 2)
+  int nbps;       // blocks per slice
+  int half0;      // half field, dir = 0
+  int half;       // half field, dir > 0: slot 0 is the compact x0
+  int e0, e1;     // extents of slots 0 and 1 in the slice's site index c0 + e0 (c1 + e1 c2)
+  int par_off;    // half fields: field parity + parity of the local origin
+  int ltab;       // entries per phase table
+};
+
+struct SGRow {
+  int64_t row;  // row of the field
+  bool ok;      // it exists and the field holds it
+  int x[3];     // local coordinates of its site along the three slots (0 where !ok)
+};
+
+// virtual row v = o * run + e of slice t; live: v is inside the block's chunk
+template <bool COORDS>
+__device__ __forceinline__ SGRow sg_row(const SGGeom& g, int t, int teff, int o, int e, bool live) {
+  SGRow r;
+  r.ok = live;
+  r.row = (static_cast<int64_t>(o) * g.Leff + teff) * g.run + e;
+  r.x[0] = r.x[1] = r.x[2] = 0;
+  if (COORDS || g.half0) {
+    const int idx = live ? o * g.inner + e / 3 : 0;
+    const int q = idx / g.e0;
+    const int c0 = idx - q * g.e0;
+    const int c2 = q / g.e1;
+    const int c1 = q - c2 * g.e1;
+    if (g.half0) r.ok = live && ((c0 + c1 + c2 + g.par_off + t) & 1) == 0;
+    r.x[0] = g.half ? 2 * c0 + ((c1 + c2 + t + g.par_off) & 1) : c0;
+    r.x[1] = c1;
+    r.x[2] = c2;
+  }
+  return r;
+}
+
+__device__ __forceinline__ double2 cmul(double2 a, double2 b) {
+  return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
+}
+// w_p of a site: the three table entries multiplied in ascending direction
+__device__ __forceinline__ double2 sg_phase(const double2* __restrict__ tab, int ltab, int p, const int x[3]) {
+  const double2* tp = tab + static_cast<int64_t>(p) * 3 * ltab;
+  return cmul(cmul(tp[x[0]], tp[ltab + x[1]]), tp[2 * ltab + x[2]]);
+}
+
+// rows of one slice, rows and sites per run
+void slice_rows(const LatticeDev& lat, int parity, int dir, int64_t* n_virtual, int64_t* run, int64_t* inner) {
+  const int L = lat.L[dir];
+  if (parity >= 0 && dir == 0) {
+    *inner = 1;
+    *run = 3;
+    *n_virtual = lat.V / L * 3;  // every (x1, x2, x3); half of them hold x0 = t
+  } else {
+    *inner = parity >= 0 ? lat.stride[dir] / 2 : lat.stride[dir];  // half: x0 is compact
+    *run = *inner * 3;
+    *n_virtual = lat.V / (lat.stride[dir] * L) * *run;
+  }
+}
+
+// the kernels' view of a launch: mu the directions != dir in ascending order (table slots 0..2)
+SGGeom slice_geom(const LatticeDev& lat, int parity, int dir, int chunk, int nbps, int ltab, const int mu[3]) {
+  int64_t n_virtual, run, inner;
+  slice_rows(lat, parity, dir, &n_virtual, &run, &inner);
+  SGGeom g{};
+  g.n_virtual = static_cast<int>(n_virtual);
+  g.run = static_cast<int>(run);
+  g.inner = static_cast<int>(inner);
+  g.chunk = chunk;
+  g.nbps = nbps;
+  g.half0 = parity >= 0 && dir == 0;
+  g.half = parity >= 0 && dir != 0;
+  g.Leff = g.half0 ? lat.L[0] / 2 : lat.L[dir];
+  g.e0 = g.half ? lat.L[0] / 2 : lat.L[mu[0]];
+  g.e1 = lat.L[mu[1]];
+  g.par_off = parity >= 0 ? parity + ((lat.origin[0] + lat.origin[1] + lat.origin[2] + lat.origin[3]) & 1) : 0;
+  g.ltab = ltab;
+  return g;
+}
+
+}  // namespace
+}  // namespace bcg

@@ -67,6 +67,42 @@ basis_matrix basis_dot(const basis& V, const block_fermion_field<N_rhs>& b) {
   return C;
 }
 
+// V^dagger b resolved by slice and momentum (bcg_basis_slice_dot): entry p * L_dir + t of the result is the K x m
+// column-major matrix tau_p(t)(i, j) = sum_{x_dir = t} w_p(x) V_i(x)^dagger b_j(x), t over the GLOBAL extent of dir
+template <int N_rhs>
+std::vector<basis_matrix> basis_slice_dot_call(const basis& V, const block_fermion_field<N_rhs>& b, int dir, int n_mom,
+                                               const int* momenta) {
+  if (dir < 0 || dir >= static_cast<int>(V.lat().dims().size())) throw std::runtime_error("basis_slice_dot: direction outside the lattice");
+  V.flush();
+  b.flush();
+  const size_t L = static_cast<size_t>(V.lat().dims()[dir]), KM = static_cast<size_t>(V.K()) * N_rhs;
+  const size_t P = n_mom > 0 ? static_cast<size_t>(n_mom) : 1;
+  std::vector<std::complex<double>> buf(P * L * KM);
+  check(bcg_basis_slice_dot(V.handles(), V.size(), b.handle(), dir, n_mom, momenta, reinterpret_cast<double*>(buf.data())),
+        V.lat().ctx(), "basis_slice_dot");
+  std::vector<basis_matrix> out(P * L);
+  for (size_t k = 0; k < P * L; ++k) out[k].assign(buf.begin() + k * KM, buf.begin() + (k + 1) * KM);
+  return out;
+}
+
+template <int N_rhs>
+std::vector<basis_matrix> basis_slice_dot(const basis& V, const block_fermion_field<N_rhs>& b, int dir) {
+  return basis_slice_dot_call(V, b, dir, 0, nullptr);
+}
+
+// momenta: integer momenta of up to 4 components each (missing ones are 0; the component along dir must be 0)
+template <int N_rhs>
+std::vector<basis_matrix> basis_slice_dot(const basis& V, const block_fermion_field<N_rhs>& b, int dir,
+                                          const std::vector<std::vector<int>>& momenta) {
+  if (momenta.empty()) throw std::runtime_error("basis_slice_dot: no momenta");
+  std::vector<int> n(4 * momenta.size(), 0);
+  for (size_t p = 0; p < momenta.size(); ++p) {
+    if (momenta[p].size() > 4) throw std::runtime_error("basis_slice_dot: a momentum has up to 4 components");
+    for (size_t mu = 0; mu < momenta[p].size(); ++mu) n[4 * p + mu] = momenta[p][mu];
+  }
+  return basis_slice_dot_call(V, b, dir, static_cast<int>(momenta.size()), n.data());
+}
+
 template <int N_rhs>
 void basis_axpy(block_fermion_field<N_rhs>& y, const basis& V, const basis_matrix& C, double beta = 1.0) {
   if (C.size() != static_cast<size_t>(V.K()) * N_rhs) throw std::invalid_argument("basis_axpy: C is K x m");

@@ -423,8 +423,33 @@ int bcg_covariant_smear(bcg_context* ctx, const bcg_gauge* g, bcg_field* f, bcg_
  * columns of dst keep their bits.  The widths may differ; full or half fields of one parity; dst != src.
  * BCG_ERR_INVALID: a NULL pointer, nv < 1, mixed contexts, parities or site counts, y among the V_k, dst == src, n < 1 or a
  * column range outside a field, a non-finite beta.  BCG_ERR_COMM (bcg_basis_dot): a divided lattice without a bcg_comm.
- * The arguments are checked before the first launch: a call that fails them leaves out / y / dst exactly as they were. */
+ * The arguments are checked before the first launch: a call that fails them leaves out / y / dst exactly as they were.
+ *
+ * bcg_basis_slice_dot: bcg_basis_dot resolved by slice and momentum,
+ *   out[((p*L_dir + t)*m + j)*K + i] = sum_{x: x_dir = t} w_p(x) sum_c conj(V_i(x,c)) b_j(x,c),
+ * V, K and the column numbering as above; w_p, momenta[4*p + mu], n_mom = 0 (the single momentum 0, no phase arithmetic),
+ * the GLOBAL t and coordinates and the host-computed phase tables exactly as in bcg_field_slice_gram.  Each (p, t) block
+ * is a K x m matrix, column-major, interleaved (re, im); every entry is computed.  Full and half fields (all operands of one
+ * parity), every width 1 .. 32 on either side, divided lattices; b may be one of the V_k; nothing is written but out.
+ * A call is a set of launches, each (a group of K_g basis columns) x (pc momenta), reading 48 (K_g + m) bytes per site.
+ * m in {16, 32} against widths in {16, 32} take the MFMA form, whose groups are runs of 16-column blocks (a 32-wide field
+ * may be split) with (K_g / 16) * pc * (m / 16) <= 4: momenta first (pc the largest of 1, 2, 4 at m = 16, of 1, 2 at m = 32,
+ * that is <= max(n_mom, 1)), then the largest group left.  Every other combination and bcg_force_generic take the generic
+ * form (pc 1 or 2, up to 32 columns).  Without momenta V = 2 x 32 columns at m = 16 is one launch with the bytes of
+ * bcg_basis_dot.  No atomics: the launch plan is fixed by shape, widths, m, parity, dir and n_mom and the block partials of
+ * a (p, t) are added in ascending order, so the same bits on every call and on every rank.  The whole P x L_dir x K x m
+ * result is assembled on the device in the buffer of bcg_basis_dot, summed over ranks with ONE bcg_comm.allreduce_sum and
+ * copied out once.  Synchronizes the stream.
+ *  - Profile keys "basis_slice_dot" (48 (K_g + m) bytes per site and launch, 8 K_g m pc flops per row), "basis_slice_fold",
+ *    "basis_slice_form_mfma" / "basis_slice_form_generic" (launch counts).
+ *  - BCG_ERR_INVALID: everything bcg_basis_dot and bcg_field_slice_gram reject -- a NULL pointer, nv < 1, mixed contexts,
+ *    parities or site counts, dir outside 0 .. ndim-1, n_mom < 0, n_mom > 0 with momenta == NULL, a non-zero momentum
+ *    component along dir or along a direction >= ndim.  BCG_ERR_COMM: a divided lattice without a bcg_comm.
+ *    BCG_ERR_UNSUPPORTED: more than 2^26 entries in all (split the momenta), or one block per slice of the smallest launch
+ *    (one block of 16 columns or one generic field, one momentum) does not fit the context's scratch.  All are returned
+ *    before the first launch and leave out untouched. */
 int bcg_basis_dot(const bcg_field* const* V, int nv, const bcg_field* b, double* out);
+int bcg_basis_slice_dot(const bcg_field* const* V, int nv, const bcg_field* b, int dir, int n_mom, const int* momenta, double* out);
 int bcg_basis_axpy(bcg_field* y, const bcg_field* const* V, int nv, const double* C, double beta);
 int bcg_field_copy_columns(bcg_field* dst, int dst_first, const bcg_field* src, int src_first, int n);
 
