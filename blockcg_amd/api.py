@@ -562,6 +562,39 @@ def basis_axpy(y, V, C, beta=1.0):
     return y
 
 
+def basis_slice_axpy(y, V, C, dir, slices=None, momentum=None, beta=1.0):
+    """y <- beta y + w V C[s] on the sites with global x_dir = slices[s] and y <- beta y on every other site
+    (bcg_basis_slice_axpy), the adjoint of basis_slice_dot.  C: an (S, K, m) array, one matrix per listed slice; slices: a
+    list of distinct global slice indices (None: all L_dir slices in ascending order, so that basis_slice_dot's result goes
+    straight in).  momentum: None (w = 1) or up to 4 integers, the entry along dir 0: w(x) = exp(+2 pi i sum_mu n_mu x_mu / L_mu)
+    of the GLOBAL coordinates.  beta exactly 0 does not read y (the other slices become zeros), beta exactly 1 leaves the other
+    slices alone.  Purely local.  y is none of V."""
+    Vh, nv, K = _basis_handles(V)
+    if not 0 <= int(dir) < y.ctx.ndim:
+        raise BlockCGError(1, "basis_slice_axpy: direction outside the lattice")
+    if slices is None:
+        S, sl, n_slices = y.ctx.dims[int(dir)], None, 0
+    else:
+        arr = np.ascontiguousarray(list(slices), dtype=np.intc)
+        if arr.ndim != 1 or arr.size == 0:
+            raise BlockCGError(1, "basis_slice_axpy: slices is a non-empty list of slice indices")
+        S, sl, n_slices = int(arr.size), arr.ctypes.data_as(_lib.c_int_p), int(arr.size)
+    C = np.asarray(C, dtype=np.complex128)
+    if C.shape != (S, K, y.N_rhs):
+        raise ValueError(f"expected {S} matrices of {K}x{y.N_rhs}")
+    Ct = np.ascontiguousarray(C.transpose(0, 2, 1))  # column-major blocks
+    mp = None
+    if momentum is not None:
+        p = list(momentum)
+        if len(p) > 4:
+            raise BlockCGError(1, "basis_slice_axpy: a momentum has up to 4 integers")
+        mom = np.zeros(4, dtype=np.intc)
+        mom[:len(p)] = p
+        mp = mom.ctypes.data_as(_lib.c_int_p)
+    y.ctx.check(y.ctx.lib.bcg_basis_slice_axpy(y.h, Vh, nv, int(dir), n_slices, sl, _dp(Ct), mp, float(beta)))
+    return y
+
+
 def deflate(B, V):
     """B <- B - V (V^dagger B) for an orthonormal basis V; returns C = V^dagger B, (K, m)."""
     C = basis_dot(V, B)

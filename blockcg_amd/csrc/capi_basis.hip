@@ -3,10 +3,12 @@
 // (bcg_field_copy_columns).  Kernels: kernels_basis.hip.  The host walks V in groups of consecutive fields (one launch per
 // group, kernels_basis.hpp); the K x m matrix lives in c->dev_basis / c->pin_basis, which grow on demand.  And the dot
 // resolved by slice and momentum (bcg_basis_slice_dot; kernels and plan: kernels_basis_slice.hip / .hpp), whose
-// P x L_dir x K x m result is assembled in the same buffer.
+// P x L_dir x K x m result is assembled in the same buffer, and its adjoint, the update by slice (bcg_basis_slice_axpy;
+// kernels and plan: kernels_basis_slice_axpy.hip / .hpp), whose matrices, phase table and slice lists are uploaded there.
 #include "capi_internal.hpp"
 #include "kernels_basis.hpp"
 #include "kernels_basis_slice.hpp"
+#include "kernels_basis_slice_axpy.hpp"
 
 namespace bcg_impl {
 namespace {
@@ -298,6 +300,109 @@ int bcg_basis_axpy(bcg_field* y, const bcg_field* const* V, int nv, const double
       }
     }
     BCG_TRY(check_launch(c, "basis_axpy"));
+    first = false;
+  }
+  return BCG_OK;
+}
+
+int bcg_basis_slice_axpy(bcg_field* y, const bcg_field* const* V, int nv, int dir, int n_slices, const int* slices, const double* C,
+                         const int* momentum, double beta) {
+  DeviceScope on_device(y ? y->ctx : nullptr);
+  const int64_t K = basis_columns(V, nv, y);
+  if (K < 0 || !C) return BCG_ERR_INVALID;
+  bcg_context* c = y->ctx;
+  for (int k = 0; k < nv; ++k)
+    if (V[k] == y) BCG_FAIL(c, BCG_ERR_INVALID, "bcg_basis_slice_axpy: y is one of the basis fields");
+  if (!std::isfinite(beta)) BCG_FAIL(c, BCG_ERR_INVALID, "bcg_basis_slice_axpy: beta is not finite");
+  if (dir < 0 || dir >= c->ndim) BCG_FAIL(c, BCG_ERR_INVALID, "bcg_basis_slice_axpy: direction outside the lattice");
+  if (n_slices < 0 || (n_slices > 0 && !slices)) BCG_FAIL(c, BCG_ERR_INVALID, "bcg_basis_slice_axpy: n_slices slices are needed");
+  const int Lg = c->gdims[dir], Ll = c->lat.L[dir], origin = c->lat.origin[dir];
+  const int S = n_slices > 0 ? n_slices : Lg;
+  // local slice -> index of its matrix in C, or -1: not listed
+  std::vector<int> index_of(Ll, -1);
+  {
+    std::vector<char> seen(Lg, 0);
+    for (int s = 0; s < S; ++s) {
+      const int t = n_slices > 0 ? slices[s] : s;
+      if (t < 0 || t >= Lg) BCG_FAIL(c, BCG_ERR_INVALID, "bcg_basis_slice_axpy: slice outside the lattice");
+      if (seen[t]) BCG_FAIL(c, BCG_ERR_INVALID, "bcg_basis_slice_axpy: a slice is listed twice");
+      seen[t] = 1;
+      if (t >= origin && t < origin + Ll) index_of[t - origin] = s;
+    }
+  }
+  if (momentum)
+    for (int mu = 0; mu < 4; ++mu)
+      if ((mu == dir || mu >= c->ndim) && momentum[mu] != 0)
+        BCG_FAIL(c, BCG_ERR_INVALID, "bcg_basis_slice_axpy: momentum component along dir or beyond the lattice's dimensions");
+  const int m = y->m;
+  if (static_cast<int64_t>(K) * m > kBasisSliceEntries / S) BCG_FAIL(c, BCG_ERR_UNSUPPORTED, "bcg_basis_slice_axpy: more than 2^26 entries");
+  const size_t entries = static_cast<size_t>(S) * K * m;
+  // the launches' lists: (local slice, index in C) of the listed slices in ascending local slice, then the other slices
+  std::vector<int> lists;
+  for (int t = 0; t < Ll; ++t)
+    if (index_of[t] >= 0) {
+      lists.push_back(t);
+      lists.push_back(index_of[t]);
+    }
+  const int nl = static_cast<int>(lists.size() / 2);
+  for (int t = 0; t < Ll; ++t)
+    if (index_of[t] < 0) lists.push_back(t);
+  const int nu = Ll - nl;
+  const bool rest = nu > 0 && beta != 1.0;
+  if (nl == 0 && !rest) return BCG_OK;  // none of the listed slices is here and the others keep their bits
+  bcg::BasisSliceAxpyPlan plan{}, plan_rest{};
+  if ((nl > 0 && !bcg::basis_slice_axpy_plan(c->lat, y->parity, dir, nl, &plan)) ||
+      (rest && !bcg::basis_slice_axpy_plan(c->lat, y->parity, dir, nu, &plan_rest)))
+    BCG_FAIL(c, BCG_ERR_UNSUPPORTED, "bcg_basis_slice_axpy: a slice of 2^30 rows or more");
+  // c->dev_basis: [C][the phase table, 3 x ltab][the lists]
+  const size_t tab_entries = momentum && nl > 0 ? static_cast<size_t>(3) * plan.ltab : 0;
+  const size_t list_entries = (lists.size() * sizeof(int) + sizeof(double2) - 1) / sizeof(double2);
+  const size_t all = entries + tab_entries + list_entries;
+  BCG_TRY(ensure_basis(c, all));
+  HIP_TRY(c, hipEventSynchronize(c->basis_uploaded));  // the previous upload has left pin_basis
+  std::memcpy(c->pin_basis, C, entries * sizeof(double2));
+  if (tab_entries) {  // w = conj(w_p) of the GLOBAL coordinates: nothing depends on the grid
+    double2* const tabs = reinterpret_cast<double2*>(c->pin_basis) + entries;
+    for (size_t e = 0; e < tab_entries; ++e) tabs[e] = make_double2(1.0, 0.0);
+    for (int s = 0; s < 3; ++s) {
+      const int mu = plan.mu[s];
+      for (int x = 0; x < c->lat.L[mu]; ++x) {
+        const double2 w = momentum_phase(momentum[mu], c->lat.origin[mu] + x, c->gdims[mu]);
+        tabs[static_cast<size_t>(s) * plan.ltab + x] = make_double2(w.x, -w.y);
+      }
+    }
+  }
+  std::memcpy(reinterpret_cast<double2*>(c->pin_basis) + entries + tab_entries, lists.data(), lists.size() * sizeof(int));
+  HIP_TRY(c, hipMemcpyAsync(c->dev_basis, c->pin_basis, all * sizeof(double2), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipEventRecord(c->basis_uploaded, c->stream));
+  const double2* const tab_dev = tab_entries ? c->dev_basis + entries : nullptr;
+  const int* const list_dev = reinterpret_cast<const int*>(c->dev_basis + entries + tab_entries);
+  if (rest) {
+    {
+      ProfScope ps(c, "basis_slice_scale", static_cast<double>(y->sites) / Ll * nu * 48.0 * (beta == 0.0 ? m : 2 * m));
+      bcg::launch_slice_scale(c->stream, m, c->lat, y->parity, dir, plan_rest, nu, list_dev + 2 * nl, y->d, beta);
+    }
+    BCG_TRY(check_launch(c, "basis_slice_scale"));
+  }
+  if (nl == 0) return BCG_OK;
+  const double sites = static_cast<double>(y->sites) / Ll * nl;  // of the listed slices
+  bool first = true;
+  for (const BasisGroup& g : basis_groups(c, V, nv, m, bcg::basis_axpy_mfma_blocks(m), 1 << 20)) {
+    const double bg = first ? beta : 1.0;
+    {
+      ProfScope ps(c, "basis_slice_axpy", sites * 48.0 * (g.K + (bg == 0.0 ? m : 2 * m)), sites * 3.0 * 8.0 * g.K * m);
+      ProfScope form(c, g.mfma ? "basis_slice_axpy_form_mfma" : "basis_slice_axpy_form_generic");
+      if (g.mfma) {
+        int n16;
+        const bcg::BasisBlocks blocks = group_blocks(V, g, &n16);
+        bcg::launch_basis_slice_axpy_mfma(c->stream, m, n16, c->lat, y->parity, dir, plan, nl, list_dev, y->d, blocks, c->dev_basis,
+                                          static_cast<int>(K), g.off, tab_dev, bg);
+      } else {
+        bcg::launch_basis_slice_axpy_generic(c->stream, m, c->lat, y->parity, dir, plan, nl, list_dev, y->d, group_fields(V, g),
+                                             c->dev_basis, static_cast<int>(K), g.off, tab_dev, bg);
+      }
+    }
+    BCG_TRY(check_launch(c, "basis_slice_axpy"));
     first = false;
   }
   return BCG_OK;

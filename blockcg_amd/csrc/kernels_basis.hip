@@ -10,13 +10,6 @@ namespace bcg {
 
 namespace {
 
-__device__ __forceinline__ void cfma(double2& acc, double2 a, double2 b) {
-  acc.x = fma(a.x, b.x, acc.x);
-  acc.x = fma(-a.y, b.y, acc.x);
-  acc.y = fma(a.x, b.y, acc.y);
-  acc.y = fma(a.y, b.x, acc.y);
-}
-
 // ---------------------------------------------------------------------------------------------
 // Dot, MFMA form.  Wave w of a block takes the quads (4 rows) w, w + 4 NW, ...; lane l owns row 4 q + (l >> 4) and column
 // l & 15 of every 16-column block of V and of b.  Accumulators: KB x (M / 16) pairs of 16 x 16 blocks, re and im.
@@ -149,35 +142,9 @@ __global__ void __launch_bounds__(256) k_basis_fold(int Kg, int m, int nblocks, 
 }
 
 // ---------------------------------------------------------------------------------------------
-// Update, MFMA form.  rmul_acc's four-product chain for a 16-column input tile and an M-column output: the rows of C that
-// belong to the block are staged at Ml[j_in * LD + 2 j_out + comp], LD = 2 M + 1 (the padded layout of MatLds<M>).
+// Update, MFMA form.  rect_acc (mfma_common.hpp): rmul_acc's four-product chain for a 16-column input tile and an M-column
+// output; the rows of C that belong to the block are staged at Ml[j_in * LD + 2 j_out + comp], LD = 2 M + 1.
 // ---------------------------------------------------------------------------------------------
-template <int M>
-__device__ __forceinline__ void rect_acc(Acc<M>& A, const Tile<16>& in, const double* Ml, int lane) {
-  constexpr int LD = MatLds<M>::LD;
-  const int kq = lane >> 4;
-  const int ar = lane & 15;
-#pragma unroll
-  for (int T = 0; T < M / 8; ++T) {
-    const int q_o = 4 * T + (ar >> 2);
-    const int s_o = q_o % (M / 4);
-    const int j_o = 4 * s_o + (ar & 3);
-    const double* base = Ml + kq * LD + 2 * j_o;
-#pragma unroll
-    for (int s_i = 0; s_i < 4; ++s_i) {
-      const double a_same = base[s_i * 4 * LD + 0];   // Re C(j_i, j_o)
-      const double a_cross = base[s_i * 4 * LD + 1];  // Im C(j_i, j_o)
-      if (T < M / 16) {
-        A.a[T] = mfma(a_same, in.v[s_i].x, A.a[T]);
-        A.a[T] = mfma_nega(a_cross, in.v[s_i].y, A.a[T]);
-      } else {
-        A.a[T] = mfma(a_cross, in.v[s_i].x, A.a[T]);
-        A.a[T] = mfma(a_same, in.v[s_i].y, A.a[T]);
-      }
-    }
-  }
-}
-
 template <int M, int KB>
 __global__ void __launch_bounds__(256) k_basis_axpy_mfma(int64_t rows, double2* __restrict__ y, BasisBlocks g,
                                                          const double2* __restrict__ C, int K, int off, double beta) {

@@ -263,6 +263,35 @@ __device__ __forceinline__ void rmul_acc2(Acc<M>& A1, const double* Ml1, Acc<M>&
   }
 }
 
+// rmul_acc's four-product chain for a 16-column input tile and an M-column output (the updates with a basis of another
+// width, kernels_basis.hip and kernels_basis_slice_axpy.hip): the 16 rows of C that belong to the input tile are staged at
+// Ml[j_in * LD + 2 j_out + comp], LD = 2 M + 1 (the padded layout of MatLds<M>).
+template <int M>
+__device__ __forceinline__ void rect_acc(Acc<M>& A, const Tile<16>& in, const double* Ml, int lane) {
+  constexpr int LD = MatLds<M>::LD;
+  const int kq = lane >> 4;
+  const int ar = lane & 15;
+#pragma unroll
+  for (int T = 0; T < M / 8; ++T) {
+    const int q_o = 4 * T + (ar >> 2);
+    const int s_o = q_o % (M / 4);
+    const int j_o = 4 * s_o + (ar & 3);
+    const double* base = Ml + kq * LD + 2 * j_o;
+#pragma unroll
+    for (int s_i = 0; s_i < 4; ++s_i) {
+      const double a_same = base[s_i * 4 * LD + 0];   // Re C(j_i, j_o)
+      const double a_cross = base[s_i * 4 * LD + 1];  // Im C(j_i, j_o)
+      if (T < M / 16) {
+        A.a[T] = mfma(a_same, in.v[s_i].x, A.a[T]);
+        A.a[T] = mfma_nega(a_cross, in.v[s_i].y, A.a[T]);
+      } else {
+        A.a[T] = mfma(a_cross, in.v[s_i].x, A.a[T]);
+        A.a[T] = mfma(a_same, in.v[s_i].y, A.a[T]);
+      }
+    }
+  }
+}
+
 // ---- Gram accumulation ---------------------------------------------------------------------------
 // Operands in (row k = l>>4, column n = l&15 [+16 jb]) ownership.  Per j-block pair (ja, jb):
 //   re(ja,jb) += a_re*b_re + a_im*b_im ;  im(ja,jb) += a_re*b_im - a_im*b_re      (conj(a) * b)

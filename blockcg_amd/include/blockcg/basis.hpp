@@ -1,9 +1,12 @@
 // blockcg/basis.hpp -- products between a solve block and a basis of another width, and deflation on top of them
-// (include/blockcg_hip.h: bcg_basis_dot, bcg_basis_axpy, bcg_field_copy_columns).
+// (include/blockcg_hip.h: bcg_basis_dot, bcg_basis_axpy, bcg_basis_slice_dot, bcg_basis_slice_axpy, bcg_field_copy_columns).
 //
 //   basis V;  V.push_back(f)                     a list of fields of any widths 1 .. 32; K = the sum of the widths
 //   basis_dot(V, b)                              C = V^dagger b, K x m column-major (element (i, j) at j * K + i)
 //   basis_axpy(y, V, C, beta = 1)                y <- beta y + V C; beta == 0 does not read y
+//   basis_slice_dot(V, b, dir[, momenta])        V^dagger b by slice of dir (and momentum): L_dir matrices K x m per momentum
+//   basis_slice_axpy(y, V, dir, slices, C, momentum, beta)   its adjoint: y <- beta y + w V C[s] on the listed slices
+//   distillation_source(y, V, dir, t0, first)    y = columns first .. of V on the slice t0, zero elsewhere
 //   copy_columns(dst, dst_first, src, src_first, n)   n columns between fields of different widths
 //   deflate(B, V)                                B <- B - V (V^dagger B); returns C = V^dagger B
 //   low_mode_solution(X, V, evals, C, sigma)     X_s += V (Lambda + sigma_s)^-1 C
@@ -15,6 +18,7 @@
 // The reference has none of these; they are extensions in the blockcg namespace, host compiler only like the other headers.
 #ifndef BLOCKCG_BASIS_HPP
 #define BLOCKCG_BASIS_HPP
+#include <algorithm>
 #include <complex>
 #include <functional>
 #include <stdexcept>
@@ -111,6 +115,42 @@ void basis_axpy(block_fermion_field<N_rhs>& y, const basis& V, const basis_matri
   check(bcg_basis_axpy(y.handle(), V.handles(), V.size(), reinterpret_cast<const double*>(C.data()), beta), V.lat().ctx(),
         "basis_axpy");
   y.device_written();
+}
+
+// The adjoint of basis_slice_dot (bcg_basis_slice_axpy): y <- beta y + w V C[s] on the sites with GLOBAL x_dir = slices[s],
+// y <- beta y on every other site.  slices empty: all L_dir slices in ascending order, so that one momentum block of
+// basis_slice_dot's result goes straight in as C.  momentum empty: w = 1; else up to 4 integers (the component along dir 0),
+// w(x) = exp(+2 pi i sum_mu n_mu x_mu / L_mu).  beta == 0 does not read y; beta == 1 leaves the other slices alone.
+template <int N_rhs>
+void basis_slice_axpy(block_fermion_field<N_rhs>& y, const basis& V, int dir, const std::vector<int>& slices,
+                      const std::vector<basis_matrix>& C, const std::vector<int>& momentum = std::vector<int>(), double beta = 1.0) {
+  if (dir < 0 || dir >= static_cast<int>(V.lat().dims().size())) throw std::runtime_error("basis_slice_axpy: direction outside the lattice");
+  const size_t S = slices.empty() ? static_cast<size_t>(V.lat().dims()[dir]) : slices.size(), KM = static_cast<size_t>(V.K()) * N_rhs;
+  if (C.size() != S) throw std::invalid_argument("basis_slice_axpy: one matrix per listed slice");
+  if (momentum.size() > 4) throw std::invalid_argument("basis_slice_axpy: a momentum has up to 4 components");
+  std::vector<std::complex<double>> buf(S * KM);
+  for (size_t s = 0; s < S; ++s) {
+    if (C[s].size() != KM) throw std::invalid_argument("basis_slice_axpy: C[s] is K x m");
+    std::copy(C[s].begin(), C[s].end(), buf.begin() + s * KM);
+  }
+  int n[4] = {0, 0, 0, 0};
+  for (size_t mu = 0; mu < momentum.size(); ++mu) n[mu] = momentum[mu];
+  V.flush();
+  y.flush();
+  check(bcg_basis_slice_axpy(y.handle(), V.handles(), V.size(), dir, static_cast<int>(slices.size()), slices.empty() ? nullptr : slices.data(),
+                             reinterpret_cast<const double*>(buf.data()), momentum.empty() ? nullptr : n, beta),
+        V.lat().ctx(), "basis_slice_axpy");
+  y.device_written();
+}
+
+// A distillation source: y_j = V_{first + j} on the slice x_dir = t0 and zero elsewhere, j < N_rhs (basis_slice_axpy with one
+// slice, beta = 0 and C the column selection)
+template <int N_rhs>
+void distillation_source(block_fermion_field<N_rhs>& y, const basis& V, int dir, int t0, int first) {
+  if (first < 0 || first + N_rhs > V.K()) throw std::invalid_argument("distillation_source: columns outside the basis");
+  std::vector<basis_matrix> C(1, basis_matrix(static_cast<size_t>(V.K()) * N_rhs));
+  for (int j = 0; j < N_rhs; ++j) C[0][static_cast<size_t>(j) * V.K() + first + j] = 1.0;
+  basis_slice_axpy(y, V, dir, std::vector<int>(1, t0), C, std::vector<int>(), 0.0);
 }
 
 template <int N_dst, int N_src>

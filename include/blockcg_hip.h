@@ -447,10 +447,41 @@ int bcg_covariant_smear(bcg_context* ctx, const bcg_gauge* g, bcg_field* f, bcg_
  *    component along dir or along a direction >= ndim.  BCG_ERR_COMM: a divided lattice without a bcg_comm.
  *    BCG_ERR_UNSUPPORTED: more than 2^26 entries in all (split the momenta), or one block per slice of the smallest launch
  *    (one block of 16 columns or one generic field, one momentum) does not fit the context's scratch.  All are returned
- *    before the first launch and leave out untouched. */
+ *    before the first launch and leave out untouched.
+ *
+ * bcg_basis_slice_axpy: the adjoint of bcg_basis_slice_dot, a basis put onto slices,
+ *   y_j(x,c) <- beta y_j(x,c) + w(x) sum_i V_i(x,c) C_s(i, j)    on the sites with GLOBAL x_dir = slices[s],
+ *   y_j(x,c) <- beta y_j(x,c)                                     on every other site,
+ * V, K and the column numbering as above; y of any width m in 1 .. 32 and none of the V_k; full and half fields (all operands
+ * of one parity), divided lattices.  slices: n_slices distinct global slice indices in 0 .. L_dir-1 in any order; n_slices = 0
+ * with slices = NULL: all L_dir slices in ascending order.  C[(s*m + j)*K + i], interleaved (re, im): one K x m column-major
+ * matrix per listed slice -- the layout of one momentum block of bcg_basis_slice_dot's out, so that with n_slices = 0 the
+ * output of that call is valid input to this one.  momentum: NULL (w = 1, no phase arithmetic) or four integers, the
+ * components along dir and beyond ndim 0; w(x) = conj(w_p(x)) = exp(+2 pi i sum_mu n_mu x_mu / L_mu) of the GLOBAL
+ * coordinates, from the tables of bcg_field_slice_gram conjugated entry by entry on the host and multiplied in ascending
+ * direction: no value depends on the process grid, and the call is the exact adjoint of bcg_basis_slice_dot at the same
+ * momentum.  A distillation source is the call with one slice, beta = 0 and C a column selection; with C = tau(t) of
+ * bcg_basis_slice_dot it is the per-slice projector V(t) V(t)^dagger b.
+ * beta exactly 0 reads no site of y (a NaN there does not survive; the slices not listed come out as exact zeros); beta
+ * exactly 1 neither reads nor writes the slices not listed; any other finite beta scales them.  Purely local: no bcg_comm
+ * call; a rank that holds none of the listed slices launches nothing at beta = 1.  Does not synchronize the stream (unless
+ * the coefficient buffer has to grow), as bcg_basis_axpy.
+ * The groups and the two forms are those of bcg_basis_axpy; a launch walks the listed local slices only, reading
+ * 48 (K_g + m) bytes per listed site; the first group's launch carries beta, the later ones run at beta = 1.  The slices not
+ * listed are one streaming launch of their own at beta != 1.  Nothing is reduced: the same bits on every call.
+ *  - Profile keys "basis_slice_axpy" (48 (K_g + 2 m) bytes per listed site and launch, 48 (K_g + m) for a first group with
+ *    beta == 0; 8 K_g m flops per row), "basis_slice_axpy_form_mfma" / "basis_slice_axpy_form_generic" (launch counts),
+ *    "basis_slice_scale" (the slices not listed).
+ *  - BCG_ERR_INVALID: everything bcg_basis_axpy rejects -- a NULL pointer, nv < 1, mixed contexts, parities or site counts,
+ *    y among the V_k, a non-finite beta -- and dir outside 0 .. ndim-1, n_slices < 0, n_slices > 0 with slices == NULL, a
+ *    slice outside 0 .. L_dir-1 or listed twice, a non-zero momentum component along dir or along a direction >= ndim.
+ *    BCG_ERR_UNSUPPORTED: more than 2^26 entries of C, or a slice of 2^30 rows or more.  All are returned before the first
+ *    launch and leave y exactly as it was. */
 int bcg_basis_dot(const bcg_field* const* V, int nv, const bcg_field* b, double* out);
 int bcg_basis_slice_dot(const bcg_field* const* V, int nv, const bcg_field* b, int dir, int n_mom, const int* momenta, double* out);
 int bcg_basis_axpy(bcg_field* y, const bcg_field* const* V, int nv, const double* C, double beta);
+int bcg_basis_slice_axpy(bcg_field* y, const bcg_field* const* V, int nv, int dir, int n_slices, const int* slices, const double* C,
+                         const int* momentum, double beta);
 int bcg_field_copy_columns(bcg_field* dst, int dst_first, const bcg_field* src, int src_first, int n);
 
 /* ---- low modes: the in-place basis rotation and the eigensolver built on it (extensions) ----------
