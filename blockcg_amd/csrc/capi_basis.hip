@@ -2,10 +2,10 @@
 // (bcg_basis_axpy) for a list V of fields whose widths sum to K != m -- and the column copy between widths
 // (bcg_field_copy_columns).  Kernels: kernels_basis.hip.  The host walks V in groups of consecutive fields (one launch per
 // group, kernels_basis.hpp); the K x m matrix lives in c->dev_basis / c->pin_basis, which grow on demand.  And the dot
-// resolved by slice and momentum (bcg_basis_slice_dot; kernels and plan: kernels_basis_slice.hip / .hpp), whose
+// resolved by slice and momentum (bcg_basis_slice_dot; kernels: kernels_basis_slice.hip, plan: slice_plan.hpp), whose
 // P x L_dir x K x m result is assembled in the same buffer, and its adjoint, the update by slice (bcg_basis_slice_axpy;
-// kernels and plan: kernels_basis_slice_axpy.hip / .hpp), whose matrices, phase table and slice lists are uploaded there.
-#include "capi_internal.hpp"
+// kernels: kernels_basis_slice_axpy.hip, plan: slice_plan.hpp), whose matrices, phase table and slice lists are uploaded there.
+#include "capi_slice.hpp"
 #include "kernels_basis.hpp"
 #include "kernels_basis_slice.hpp"
 #include "kernels_basis_slice_axpy.hpp"
@@ -13,9 +13,8 @@
 namespace bcg_impl {
 namespace {
 
-// bcg_basis_slice_dot: the phase tables and the block partials take the first half of c->partials (ensure_scratch), as in
+// bcg_basis_slice_dot: the phase tables and the block partials take the first half of c->partials (kSliceHalf), as in
 // bcg_field_slice_gram; the whole result, P x L_dir x K x m, is at most 2^26 entries (1 GiB) of c->dev_basis
-constexpr int64_t kBasisSliceHalf = static_cast<int64_t>(kMaxGramBlocks) * 32 * 32 / 2;
 constexpr int64_t kBasisSliceEntries = static_cast<int64_t>(1) << 26;
 
 struct BasisGroup {
@@ -105,6 +104,19 @@ int ensure_basis(bcg_context* c, size_t entries) {
   return BCG_OK;
 }
 
+// the result assembled in c->dev_basis: summed over ranks, then to `out` through c->pin_basis
+int download_basis(bcg_context* c, size_t entries, double* out) {
+  if (c->distributed) {
+    ProfScope ps(c, "allreduce");
+    if (c->comm.allreduce_sum(c->comm.user, c->dev_basis, 2 * entries) != 0) BCG_FAIL(c, BCG_ERR_COMM, "allreduce_sum callback failed");
+  }
+  HIP_TRY(c, hipEventSynchronize(c->basis_uploaded));  // an upload of bcg_basis_axpy may still read pin_basis
+  HIP_TRY(c, hipMemcpyAsync(c->pin_basis, c->dev_basis, entries * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
+  BCG_TRY(stream_sync(c));
+  std::memcpy(out, c->pin_basis, entries * sizeof(double2));
+  return BCG_OK;
+}
+
 }  // namespace
 }  // namespace bcg_impl
 
@@ -151,15 +163,7 @@ int bcg_basis_dot(const bcg_field* const* V, int nv, const bcg_field* b, double*
     }
     BCG_TRY(check_launch(c, "basis_fold"));
   }
-  if (c->distributed) {
-    ProfScope ps(c, "allreduce");
-    if (c->comm.allreduce_sum(c->comm.user, c->dev_basis, 2 * entries) != 0) BCG_FAIL(c, BCG_ERR_COMM, "allreduce_sum callback failed");
-  }
-  HIP_TRY(c, hipEventSynchronize(c->basis_uploaded));  // an upload of bcg_basis_axpy may still read pin_basis
-  HIP_TRY(c, hipMemcpyAsync(c->pin_basis, c->dev_basis, entries * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
-  BCG_TRY(stream_sync(c));
-  std::memcpy(out, c->pin_basis, entries * sizeof(double2));
-  return BCG_OK;
+  return download_basis(c, entries, out);
 }
 
 int bcg_basis_slice_dot(const bcg_field* const* V, int nv, const bcg_field* b, int dir, int n_mom, const int* momenta, double* out) {
@@ -167,12 +171,8 @@ int bcg_basis_slice_dot(const bcg_field* const* V, int nv, const bcg_field* b, i
   const int64_t K = basis_columns(V, nv, b);
   if (K < 0 || !out) return BCG_ERR_INVALID;
   bcg_context* c = b->ctx;
-  if (dir < 0 || dir >= c->ndim) BCG_FAIL(c, BCG_ERR_INVALID, "bcg_basis_slice_dot: direction outside the lattice");
-  if (n_mom < 0 || (n_mom > 0 && !momenta)) BCG_FAIL(c, BCG_ERR_INVALID, "bcg_basis_slice_dot: n_mom momenta are needed");
-  for (int p = 0; p < n_mom; ++p)
-    for (int mu = 0; mu < 4; ++mu)
-      if ((mu == dir || mu >= c->ndim) && momenta[4 * p + mu] != 0)
-        BCG_FAIL(c, BCG_ERR_INVALID, "bcg_basis_slice_dot: momentum component along dir or beyond the lattice's dimensions");
+  BCG_TRY(check_slice_dir(c, "bcg_basis_slice_dot", dir));
+  BCG_TRY(check_slice_momenta(c, "bcg_basis_slice_dot", dir, n_mom, momenta));
   if (c->distributed && (!c->have_comm || !c->comm.allreduce_sum))
     BCG_FAIL(c, BCG_ERR_COMM, "lattice is split over ranks but no bcg_comm was set");
   const int m = b->m;
@@ -184,7 +184,7 @@ int bcg_basis_slice_dot(const bcg_field* const* V, int nv, const bcg_field* b, i
   std::vector<int> widths(nv);
   for (int k = 0; k < nv; ++k) widths[k] = V[k]->m;
   bcg::BasisSlicePlan plan;
-  if (!bcg::basis_slice_plan(widths.data(), nv, m, !c->force_generic, c->lat, b->parity, dir, n_mom, kBasisSliceHalf, &plan))
+  if (!bcg::basis_slice_plan(widths.data(), nv, m, !c->force_generic, c->lat, b->parity, dir, n_mom, kSliceHalf, &plan))
     BCG_FAIL(c, BCG_ERR_UNSUPPORTED, "bcg_basis_slice_dot: one launch does not fit the context's scratch");
   int rc = ensure_scratch(c);
   if (rc == BCG_OK) rc = ensure_basis(c, entries);
@@ -196,18 +196,10 @@ int bcg_basis_slice_dot(const bcg_field* const* V, int nv, const bcg_field* b, i
   // c->partials, first half: [phase tables][block partials]; the result is assembled in c->dev_basis
   double2* const tab_dev = c->partials;
   double2* const partials = c->partials + (n_mom > 0 ? bcg::basis_slice_table_entries(plan) : 0);
-  // the tables of every momentum (a launch's unused momenta: ones), from global coordinates: nothing depends on the grid
-  std::vector<double2> tabs;
-  const int64_t per_tab = static_cast<int64_t>(3) * plan.ltab;
-  if (n_mom > 0) {
-    tabs.assign(static_cast<size_t>(per_tab) * (P + plan.pc_max()), make_double2(1.0, 0.0));
-    for (int p = 0; p < P; ++p)
-      for (int s = 0; s < 3; ++s) {
-        const int mu = plan.mu[s];
-        for (int x = 0; x < c->lat.L[mu]; ++x)
-          tabs[p * per_tab + static_cast<int64_t>(s) * plan.ltab + x] = momentum_phase(momenta[4 * p + mu], c->lat.origin[mu] + x, c->gdims[mu]);
-      }
-  }
+  // the tables of every momentum, and those of a launch's unused momenta
+  const int64_t per_tab = static_cast<int64_t>(3) * plan.walk.ltab;
+  std::vector<double2> tabs(n_mom > 0 ? static_cast<size_t>(per_tab) * (P + plan.pc_max()) : 0);
+  if (n_mom > 0) slice_phase_tables(c, plan.walk, momenta, P, plan.pc_max(), false, tabs.data());
   if (c->lat.split[dir])  // the slices of the other ranks: zeros from this one
     HIP_TRY(c, hipMemsetAsync(c->dev_basis, 0, entries * sizeof(double2), c->stream));
   // the 16-column blocks of the MFMA fields of V, in order: an MFMA group is a run of them
@@ -234,10 +226,8 @@ int bcg_basis_slice_dot(const bcg_field* const* V, int nv, const bcg_field* b, i
     }
     for (int p0 = 0; p0 < P; p0 += pc_g) {
       const int n = std::min(pc_g, P - p0);
-      const int pc = bcg::basis_slice_launch_pc(n);
-      if (n_mom > 0)
-        HIP_TRY(c, hipMemcpyAsync(tab_dev, tabs.data() + p0 * per_tab, static_cast<size_t>(pc * per_tab) * sizeof(double2),
-                                  hipMemcpyHostToDevice, c->stream));
+      const int pc = bcg::slice_launch_pc(n);
+      if (n_mom > 0) BCG_TRY(upload_slice_tables(c, tab_dev, tabs, per_tab, p0, pc));
       {
         ProfScope ps(c, "basis_slice_dot", static_cast<double>(b->sites) * 48.0 * (g.K + m), static_cast<double>(rows_of(b)) * 8.0 * g.K * m * pc);
         ProfScope form(c, g.mfma ? "basis_slice_form_mfma" : "basis_slice_form_generic");
@@ -251,21 +241,13 @@ int bcg_basis_slice_dot(const bcg_field* const* V, int nv, const bcg_field* b, i
       BCG_TRY(check_launch(c, "basis_slice_dot"));
       {
         ProfScope ps(c, "basis_slice_fold");
-        bcg::launch_basis_slice_fold(c->stream, g.K, m, pc, n, Ll, Lg, plan.nbps, c->lat.origin[dir], static_cast<int>(K), g.off, p0, partials,
+        bcg::launch_basis_slice_fold(c->stream, g.K, m, pc, n, Ll, Lg, plan.walk.nbps, c->lat.origin[dir], static_cast<int>(K), g.off, p0, partials,
                                      c->dev_basis);
       }
       BCG_TRY(check_launch(c, "basis_slice_fold"));
     }
   }
-  if (c->distributed) {
-    ProfScope ps(c, "allreduce");
-    if (c->comm.allreduce_sum(c->comm.user, c->dev_basis, 2 * entries) != 0) BCG_FAIL(c, BCG_ERR_COMM, "allreduce_sum callback failed");
-  }
-  HIP_TRY(c, hipEventSynchronize(c->basis_uploaded));  // an upload of bcg_basis_axpy may still read pin_basis
-  HIP_TRY(c, hipMemcpyAsync(c->pin_basis, c->dev_basis, entries * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
-  BCG_TRY(stream_sync(c));
-  std::memcpy(out, c->pin_basis, entries * sizeof(double2));
-  return BCG_OK;
+  return download_basis(c, entries, out);
 }
 
 int bcg_basis_axpy(bcg_field* y, const bcg_field* const* V, int nv, const double* C, double beta) {
@@ -314,7 +296,7 @@ int bcg_basis_slice_axpy(bcg_field* y, const bcg_field* const* V, int nv, int di
   for (int k = 0; k < nv; ++k)
     if (V[k] == y) BCG_FAIL(c, BCG_ERR_INVALID, "bcg_basis_slice_axpy: y is one of the basis fields");
   if (!std::isfinite(beta)) BCG_FAIL(c, BCG_ERR_INVALID, "bcg_basis_slice_axpy: beta is not finite");
-  if (dir < 0 || dir >= c->ndim) BCG_FAIL(c, BCG_ERR_INVALID, "bcg_basis_slice_axpy: direction outside the lattice");
+  BCG_TRY(check_slice_dir(c, "bcg_basis_slice_axpy", dir));
   if (n_slices < 0 || (n_slices > 0 && !slices)) BCG_FAIL(c, BCG_ERR_INVALID, "bcg_basis_slice_axpy: n_slices slices are needed");
   const int Lg = c->gdims[dir], Ll = c->lat.L[dir], origin = c->lat.origin[dir];
   const int S = n_slices > 0 ? n_slices : Lg;
@@ -330,10 +312,7 @@ int bcg_basis_slice_axpy(bcg_field* y, const bcg_field* const* V, int nv, int di
       if (t >= origin && t < origin + Ll) index_of[t - origin] = s;
     }
   }
-  if (momentum)
-    for (int mu = 0; mu < 4; ++mu)
-      if ((mu == dir || mu >= c->ndim) && momentum[mu] != 0)
-        BCG_FAIL(c, BCG_ERR_INVALID, "bcg_basis_slice_axpy: momentum component along dir or beyond the lattice's dimensions");
+  BCG_TRY(check_slice_momenta(c, "bcg_basis_slice_axpy", dir, momentum ? 1 : 0, momentum));
   const int m = y->m;
   if (static_cast<int64_t>(K) * m > kBasisSliceEntries / S) BCG_FAIL(c, BCG_ERR_UNSUPPORTED, "bcg_basis_slice_axpy: more than 2^26 entries");
   const size_t entries = static_cast<size_t>(S) * K * m;
@@ -350,7 +329,7 @@ int bcg_basis_slice_axpy(bcg_field* y, const bcg_field* const* V, int nv, int di
   const int nu = Ll - nl;
   const bool rest = nu > 0 && beta != 1.0;
   if (nl == 0 && !rest) return BCG_OK;  // none of the listed slices is here and the others keep their bits
-  bcg::BasisSliceAxpyPlan plan{}, plan_rest{};
+  bcg::SliceWalk plan{}, plan_rest{};
   if ((nl > 0 && !bcg::basis_slice_axpy_plan(c->lat, y->parity, dir, nl, &plan)) ||
       (rest && !bcg::basis_slice_axpy_plan(c->lat, y->parity, dir, nu, &plan_rest)))
     BCG_FAIL(c, BCG_ERR_UNSUPPORTED, "bcg_basis_slice_axpy: a slice of 2^30 rows or more");
@@ -361,17 +340,8 @@ int bcg_basis_slice_axpy(bcg_field* y, const bcg_field* const* V, int nv, int di
   BCG_TRY(ensure_basis(c, all));
   HIP_TRY(c, hipEventSynchronize(c->basis_uploaded));  // the previous upload has left pin_basis
   std::memcpy(c->pin_basis, C, entries * sizeof(double2));
-  if (tab_entries) {  // w = conj(w_p) of the GLOBAL coordinates: nothing depends on the grid
-    double2* const tabs = reinterpret_cast<double2*>(c->pin_basis) + entries;
-    for (size_t e = 0; e < tab_entries; ++e) tabs[e] = make_double2(1.0, 0.0);
-    for (int s = 0; s < 3; ++s) {
-      const int mu = plan.mu[s];
-      for (int x = 0; x < c->lat.L[mu]; ++x) {
-        const double2 w = momentum_phase(momentum[mu], c->lat.origin[mu] + x, c->gdims[mu]);
-        tabs[static_cast<size_t>(s) * plan.ltab + x] = make_double2(w.x, -w.y);
-      }
-    }
-  }
+  if (tab_entries)  // w = conj(w_p)
+    slice_phase_tables(c, plan, momentum, 1, 0, true, reinterpret_cast<double2*>(c->pin_basis) + entries);
   std::memcpy(reinterpret_cast<double2*>(c->pin_basis) + entries + tab_entries, lists.data(), lists.size() * sizeof(int));
   HIP_TRY(c, hipMemcpyAsync(c->dev_basis, c->pin_basis, all * sizeof(double2), hipMemcpyHostToDevice, c->stream));
   HIP_TRY(c, hipEventRecord(c->basis_uploaded, c->stream));

@@ -2,16 +2,12 @@
 // (bcg_field_fill_noise), point and wall sources (bcg_field_set_point_sources, bcg_field_set_wall_sources) and the inner
 // product per slice and column (bcg_field_slice_dot); and the per-slice Gram matrices with momentum projection
 // (bcg_field_slice_gram).  Kernels: kernels_sources.hip, kernels_slice_gram.hip.
-#include "capi_internal.hpp"
+#include "capi_slice.hpp"
 #include "kernels_slice_gram.hpp"
 #include "kernels_sources.hpp"
 
 namespace bcg_impl {
 namespace {
-
-// c->partials (ensure_scratch) as the slice dot uses it: block partials in the first half, the reduced [L_dir global][m]
-// result, all-reduced in place, in the second
-constexpr int64_t kSliceHalf = static_cast<int64_t>(kMaxGramBlocks) * 32 * 32 / 2;
 
 bool colours_ok(const int* colour, int m) {
   for (int j = 0; j < m; ++j)
@@ -80,7 +76,7 @@ int bcg_field_set_wall_sources(bcg_field* f, int dir, const int* slice, const in
   DeviceScope on_device(f ? f->ctx : nullptr);
   if (!f || !slice || !colour) return BCG_ERR_INVALID;
   bcg_context* c = f->ctx;
-  if (dir < 0 || dir >= c->ndim) BCG_FAIL(c, BCG_ERR_INVALID, "bcg_field_set_wall_sources: direction outside the lattice");
+  BCG_TRY(check_slice_dir(c, "bcg_field_set_wall_sources", dir));
   if (!colours_ok(colour, f->m)) BCG_FAIL(c, BCG_ERR_INVALID, "bcg_field_set_wall_sources: colour outside 0..2");
   if (site_parity < -1 || site_parity > 1 || (f->parity >= 0 && site_parity >= 0 && site_parity != f->parity))
     BCG_FAIL(c, BCG_ERR_INVALID, "bcg_field_set_wall_sources: site_parity must be -1, 0 or 1, and a half field's own");
@@ -102,7 +98,7 @@ int bcg_field_slice_dot(const bcg_field* a, const bcg_field* b, int dir, double*
   DeviceScope on_device(a ? a->ctx : nullptr);
   if (!same_shape(a, b) || !out) return BCG_ERR_INVALID;
   bcg_context* c = a->ctx;
-  if (dir < 0 || dir >= c->ndim) BCG_FAIL(c, BCG_ERR_INVALID, "bcg_field_slice_dot: direction outside the lattice");
+  BCG_TRY(check_slice_dir(c, "bcg_field_slice_dot", dir));
   const int m = a->m;
   const int64_t n_out = static_cast<int64_t>(c->gdims[dir]) * m;
   if (n_out > kSliceHalf) BCG_FAIL(c, BCG_ERR_UNSUPPORTED, "bcg_field_slice_dot: too many slices for the context's scratch");
@@ -136,12 +132,8 @@ int bcg_field_slice_gram(const bcg_field* a, const bcg_field* b, int dir, int n_
   DeviceScope on_device(a ? a->ctx : nullptr);
   if (!same_shape(a, b) || !out) return BCG_ERR_INVALID;
   bcg_context* c = a->ctx;
-  if (dir < 0 || dir >= c->ndim) BCG_FAIL(c, BCG_ERR_INVALID, "bcg_field_slice_gram: direction outside the lattice");
-  if (n_mom < 0 || (n_mom > 0 && !momenta)) BCG_FAIL(c, BCG_ERR_INVALID, "bcg_field_slice_gram: n_mom momenta are needed");
-  for (int p = 0; p < n_mom; ++p)
-    for (int mu = 0; mu < 4; ++mu)
-      if ((mu == dir || mu >= c->ndim) && momenta[4 * p + mu] != 0)
-        BCG_FAIL(c, BCG_ERR_INVALID, "bcg_field_slice_gram: momentum component along dir or beyond the lattice's dimensions");
+  BCG_TRY(check_slice_dir(c, "bcg_field_slice_gram", dir));
+  BCG_TRY(check_slice_momenta(c, "bcg_field_slice_gram", dir, n_mom, momenta));
   if (c->distributed && (!c->have_comm || !c->comm.allreduce_sum))
     BCG_FAIL(c, BCG_ERR_COMM, "lattice is split over ranks but no bcg_comm was set");
   const int m = a->m;
@@ -158,24 +150,14 @@ int bcg_field_slice_gram(const bcg_field* a, const bcg_field* b, int dir, int n_
   double2* const partials = c->partials + tab_entries;
   double2* const reduced = c->partials + kSliceHalf;
   const int P = n_mom > 0 ? n_mom : 1;
-  // the tables of every momentum (a launch's unused momenta: ones), from global coordinates: nothing depends on the grid
-  std::vector<double2> tabs;
-  const int64_t per_tab = static_cast<int64_t>(3) * plan.ltab;
-  if (n_mom > 0) {
-    tabs.assign(static_cast<size_t>(per_tab) * (P + plan.pc), make_double2(1.0, 0.0));
-    for (int p = 0; p < P; ++p)
-      for (int s = 0; s < 3; ++s) {
-        const int mu = plan.mu[s];
-        for (int x = 0; x < c->lat.L[mu]; ++x)
-          tabs[p * per_tab + static_cast<int64_t>(s) * plan.ltab + x] = momentum_phase(momenta[4 * p + mu], c->lat.origin[mu] + x, c->gdims[mu]);
-      }
-  }
+  // the tables of every momentum, and those of a launch's unused momenta
+  const int64_t per_tab = static_cast<int64_t>(3) * plan.walk.ltab;
+  std::vector<double2> tabs(n_mom > 0 ? static_cast<size_t>(per_tab) * (P + plan.pc) : 0);
+  if (n_mom > 0) slice_phase_tables(c, plan.walk, momenta, P, plan.pc, false, tabs.data());
   for (int p0 = 0; p0 < P; p0 += plan.pc) {
     const int n = std::min(plan.pc, P - p0);
-    const int pc = bcg::slice_gram_launch_pc(n);
-    if (n_mom > 0)
-      HIP_TRY(c, hipMemcpyAsync(tab_dev, tabs.data() + p0 * per_tab, static_cast<size_t>(pc * per_tab) * sizeof(double2),
-                                hipMemcpyHostToDevice, c->stream));
+    const int pc = bcg::slice_launch_pc(n);
+    if (n_mom > 0) BCG_TRY(upload_slice_tables(c, tab_dev, tabs, per_tab, p0, pc));
     {
       ProfScope ps(c, "slice_gram", row_bytes(a, a == b ? 1 : 2), product_flops(a, pc));
       bcg::launch_slice_gram(c->stream, m, mfma, c->lat, a->parity, dir, plan, pc, a->d, b->d, n_mom > 0 ? tab_dev : nullptr, partials);
@@ -186,7 +168,7 @@ int bcg_field_slice_gram(const bcg_field* a, const bcg_field* b, int dir, int n_
       HIP_TRY(c, hipMemsetAsync(reduced, 0, n_red * sizeof(double2), c->stream));
     {
       ProfScope ps(c, "slice_gram_fold");
-      bcg::launch_slice_gram_fold(c->stream, m, pc, n, c->lat.L[dir], Lg, plan.nbps, c->lat.origin[dir], partials, reduced);
+      bcg::launch_slice_gram_fold(c->stream, m, pc, n, c->lat.L[dir], Lg, plan.walk.nbps, c->lat.origin[dir], partials, reduced);
     }
     BCG_TRY(check_launch(c, "slice_gram_fold"));
     if (c->distributed) {

@@ -3,6 +3,7 @@
 // (update) of mfma_common.hpp, restated here for (16 k, m) blocks instead of square ones; four real products per complex
 // one.  Generic form: lane = (row, output column) with the rows of a tile staged in LDS.  Plain stores, no atomics; 64-bit
 // wherever an element offset is formed.
+#include "complex_ops.hpp"
 #include "kernels_basis.hpp"
 #include "mfma_common.hpp"
 

@@ -39,23 +39,7 @@ struct BasisFields {  // generic form: field k has w[k] columns, the group's col
 
 inline bool basis_mfma_width(int w) { return w == 16 || w == 32; }
 
-namespace {  // device helpers of the generic form, shared by kernels_basis.hip and kernels_basis_slice*.hip
-
-// acc += a b
-__device__ __forceinline__ void cfma(double2& acc, double2 a, double2 b) {
-  acc.x = fma(a.x, b.x, acc.x);
-  acc.x = fma(-a.y, b.y, acc.x);
-  acc.y = fma(a.x, b.y, acc.y);
-  acc.y = fma(a.y, b.x, acc.y);
-}
-
-// acc += conj(a) b
-__device__ __forceinline__ void cfma_conj(double2& acc, double2 a, double2 b) {
-  acc.x = fma(a.x, b.x, acc.x);
-  acc.x = fma(a.y, b.y, acc.x);
-  acc.y = fma(a.x, b.y, acc.y);
-  acc.y = fma(-a.y, b.x, acc.y);
-}
+namespace {  // device helper of the generic form, shared by kernels_basis.hip and kernels_basis_slice*.hip
 
 // the field that holds column i of a generic group: selects over the (few) fields, no indexed access to the argument
 __device__ __forceinline__ const double2* basis_column(const BasisFields& g, int i, int* w, int* o) {

@@ -24,10 +24,9 @@ __global__ void __launch_bounds__(256) k_basis_slice_dot_mfma(SGGeom g, BasisBlo
   static_assert(KB * PC * JB <= 4, "64 accumulator registers at the most");
   __shared__ __attribute__((aligned(16))) double red[NW * 8 * 64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int t = blockIdx.x / g.nbps, k = blockIdx.x - t * g.nbps;
-  const int teff = g.half0 ? t >> 1 : t;
-  const int r0 = k * g.chunk;
-  const int r1 = r0 + g.chunk < g.n_virtual ? r0 + g.chunk : g.n_virtual;
+  const int t = blockIdx.x / g.nbps;
+  const SGBlock bk = sg_block(g, t, t);
+  const int teff = bk.teff, r0 = bk.r0, r1 = bk.r1;
   const int nq = (r1 - r0 + 3) >> 2;
   const int col = lane & 15;
   d4 re[PC][NT], im[PC][NT];
@@ -128,36 +127,26 @@ __global__ void __launch_bounds__(256) k_basis_slice_dot_generic(int m, SGGeom g
   __shared__ double2 As[R * kBasisGenericCols];
   __shared__ double2 Bs[PC][R * 32];
   const int tid = threadIdx.x;
-  const int t = blockIdx.x / g.nbps, k = blockIdx.x - t * g.nbps;
-  const int teff = g.half0 ? t >> 1 : t;
-  const int r0 = k * g.chunk;
-  const int r1 = r0 + g.chunk < g.n_virtual ? r0 + g.chunk : g.n_virtual;
+  const int t = blockIdx.x / g.nbps;
+  const SGBlock bk = sg_block(g, t, t);
   const int Kg = v.K, P = Kg * m;
   double2 acc[PC][NPT];
 #pragma unroll
   for (int p = 0; p < PC; ++p)
 #pragma unroll
     for (int q = 0; q < NPT; ++q) acc[p][q] = make_double2(0.0, 0.0);
-  for (int base = r0; base < r1; base += R) {
+  for (int base = bk.r0; base < bk.r1; base += R) {
     __syncthreads();
     for (int x = tid; x < R * Kg; x += 256) {
       const int r = x / Kg, i = x - r * Kg;
-      const int vr = base + r;
-      const bool live = vr < r1;
-      const int vv = live ? vr : r0;
-      const int o = vv / g.run, e = vv - o * g.run;
-      const SGRow rw = sg_row<false>(g, t, teff, o, e, live);
+      const SGRow rw = sg_row_at<false>(g, bk, base + r);
       int w, off;
       const double2* f = basis_column(v, i, &w, &off);
       As[x] = rw.ok ? f[rw.row * w + (i - off)] : make_double2(0.0, 0.0);
     }
     for (int x = tid; x < R * m; x += 256) {
       const int r = x / m, j = x - r * m;
-      const int vr = base + r;
-      const bool live = vr < r1;
-      const int vv = live ? vr : r0;
-      const int o = vv / g.run, e = vv - o * g.run;
-      const SGRow rw = sg_row<PHASE>(g, t, teff, o, e, live);
+      const SGRow rw = sg_row_at<PHASE>(g, bk, base + r);
       const double2 bv = rw.ok ? b[rw.row * m + j] : make_double2(0.0, 0.0);
 #pragma unroll
       for (int p = 0; p < PC; ++p) Bs[p][x] = PHASE ? cmul(bv, sg_phase(tab, g.ltab, p, rw.x)) : bv;
@@ -220,109 +209,12 @@ void slice_dot_mfma(hipStream_t s, unsigned blocks, int pc, const SGGeom& g, con
   }
 }
 
-int mfma_pc(int m, int P) { return m == 16 && P >= 4 ? 4 : P >= 2 ? 2 : 1; }
-
-// the groups of a call: MFMA runs cut into kb blocks, generic runs into groups of at most `cols` columns
-std::vector<BasisSliceGroup> slice_groups(const int* widths, int nv, bool fast, int kb, int cols) {
-  std::vector<BasisSliceGroup> out;
-  int off = 0, block = 0;
-  for (int k = 0; k < nv;) {
-    const bool mf = fast && basis_mfma_width(widths[k]);
-    if (mf) {
-      int nb = 0;
-      for (; k < nv && basis_mfma_width(widths[k]); ++k) nb += widths[k] / 16;
-      for (int q = 0; q < nb; q += kb) {
-        const int n = nb - q < kb ? nb - q : kb;
-        out.push_back(BasisSliceGroup{true, block + q, n, 16 * n, off + 16 * q});
-      }
-      block += nb;
-      off += 16 * nb;
-    } else {
-      BasisSliceGroup g{false, k, 0, 0, off};
-      while (k < nv && !(fast && basis_mfma_width(widths[k])) && g.count < kBasisGenericFields &&
-             (g.count == 0 || g.K + widths[k] <= cols)) {
-        g.K += widths[k];
-        g.count += 1;
-        k += 1;
-      }
-      off += g.K;
-      out.push_back(g);
-    }
-  }
-  return out;
-}
-
 }  // namespace
-
-int BasisSlicePlan::pc_max() const {
-  int pc = 1;
-  for (const BasisSliceGroup& g : groups) pc = pc_of(g) > pc ? pc_of(g) : pc;
-  return pc;
-}
-
-int basis_slice_launch_pc(int n) { return n <= 1 ? 1 : n <= 2 ? 2 : 4; }
-
-bool basis_slice_plan(const int* widths, int nv, int m, bool fast, const LatticeDev& lat, int parity, int dir, int n_mom,
-                      int64_t half_entries, BasisSlicePlan* plan) {
-  fast = fast && (m == 16 || m == 32);
-  const int L = lat.L[dir];
-  int n = 0;
-  plan->ltab = 1;
-  for (int mu = 0; mu < 4; ++mu)
-    if (mu != dir) {
-      plan->mu[n++] = mu;
-      if (lat.L[mu] > plan->ltab) plan->ltab = lat.L[mu];
-    }
-  int64_t n_virtual, run, inner;
-  slice_rows(lat, parity, dir, &n_virtual, &run, &inner);
-  if (n_virtual >= (int64_t(1) << 30)) return false;
-  const int64_t most = (n_virtual + 63) / 64;
-  const int64_t want = std::max<int64_t>(L, std::min<int64_t>(256, L * most));
-  const int P = n_mom > 0 ? n_mom : 1;
-  plan->pc_mfma = fast ? mfma_pc(m, P) : 1;
-  plan->kb = fast ? 4 / (plan->pc_mfma * (m / 16)) : 1;
-  plan->pc_generic = P >= 2 ? 2 : 1;
-  plan->cols = kBasisGenericCols;
-  int64_t budget;
-  for (;;) {
-    plan->groups = slice_groups(widths, nv, fast, plan->kb, plan->cols);
-    int64_t E = 0;
-    const BasisSliceGroup* top = nullptr;
-    for (const BasisSliceGroup& g : plan->groups) {
-      const int64_t e = static_cast<int64_t>(plan->pc_of(g)) * g.K * m;
-      if (e > E) {
-        E = e;
-        top = &g;
-      }
-    }
-    const int64_t room = half_entries - (n_mom > 0 ? basis_slice_table_entries(*plan) : 0);
-    budget = room > 0 ? room / E : 0;
-    if (budget >= want) break;
-    if (top->mfma) {
-      if (plan->kb > 1) plan->kb -= 1;
-      else if (plan->pc_mfma > 1) plan->pc_mfma /= 2;
-      else break;
-    } else {
-      if (top->count > 1) plan->cols = top->K / 2;
-      else if (plan->pc_generic > 1) plan->pc_generic = 1;
-      else break;
-    }
-  }
-  if (budget < L) return false;
-  if (budget > 2048) budget = 2048;
-  int64_t nbps = budget / L;
-  if (nbps > most) nbps = most;
-  const int64_t chunk = ((n_virtual + nbps - 1) / nbps + 15) / 16 * 16;
-  nbps = (n_virtual + chunk - 1) / chunk;
-  plan->nbps = static_cast<int>(nbps);
-  plan->chunk = static_cast<int>(chunk);
-  return true;
-}
 
 void launch_basis_slice_dot_mfma(hipStream_t s, int m, int kb, const LatticeDev& lat, int parity, int dir, const BasisSlicePlan& plan,
                                  int pc, const BasisBlocks& v, const double2* b, const double2* tab, double2* partials) {
-  const SGGeom g = slice_geom(lat, parity, dir, plan.chunk, plan.nbps, plan.ltab, plan.mu);
-  const unsigned blocks = static_cast<unsigned>(plan.nbps) * static_cast<unsigned>(lat.L[dir]);
+  const SGGeom g = slice_geom(lat, parity, dir, plan.walk);
+  const unsigned blocks = static_cast<unsigned>(plan.walk.nbps) * static_cast<unsigned>(lat.L[dir]);
   if (m == 16) {
     switch (kb) {
       case 1: slice_dot_mfma<16, 1>(s, blocks, pc, g, v, b, tab, partials); break;
@@ -338,8 +230,8 @@ void launch_basis_slice_dot_mfma(hipStream_t s, int m, int kb, const LatticeDev&
 
 void launch_basis_slice_dot_generic(hipStream_t s, int m, const LatticeDev& lat, int parity, int dir, const BasisSlicePlan& plan,
                                     int pc, const BasisFields& v, const double2* b, const double2* tab, double2* partials) {
-  const SGGeom g = slice_geom(lat, parity, dir, plan.chunk, plan.nbps, plan.ltab, plan.mu);
-  const unsigned blocks = static_cast<unsigned>(plan.nbps) * static_cast<unsigned>(lat.L[dir]);
+  const SGGeom g = slice_geom(lat, parity, dir, plan.walk);
+  const unsigned blocks = static_cast<unsigned>(plan.walk.nbps) * static_cast<unsigned>(lat.L[dir]);
   if (!tab) hipLaunchKernelGGL((k_basis_slice_dot_generic<1, false>), dim3(blocks), dim3(256), 0, s, m, g, v, b, tab, partials);
   else if (pc == 1) hipLaunchKernelGGL((k_basis_slice_dot_generic<1, true>), dim3(blocks), dim3(256), 0, s, m, g, v, b, tab, partials);
   else hipLaunchKernelGGL((k_basis_slice_dot_generic<2, true>), dim3(blocks), dim3(256), 0, s, m, g, v, b, tab, partials);

@@ -3,7 +3,7 @@
 //   tau_p(t)(i, j) = sum_{x : x_dir = t} w_p(x) sum_c conj(V_i[x, c]) b[x, c, j]       over the LOCAL sites,
 //
 // V a list of fields whose widths sum to K, b of width m.  The rows of a slice are walked as the per-slice Gram kernels walk
-// them (slice_walk.hpp, described in kernels_slice_gram.hpp), the operands of a launch are a GROUP of basis columns as in
+// them (slice_walk.hpp, described in slice_plan.hpp), the operands of a launch are a GROUP of basis columns as in
 // the whole-lattice products (kernels_basis.hpp).  A call is a set of launches, each (group of K_g basis columns) x (pc
 // momenta); a launch reads 48 (K_g + m) bytes per site, a call ceil(K / K_g) ceil(P / pc) 48 (K_g + m).
 //
@@ -17,16 +17,15 @@
 //            (BasisFields), a field alone where it is wider than `cols`.  Instantiated pc: 1, 2.
 // A run of fields of one form ends where the form changes; one call may use both.
 //
-// The launch plan (basis_slice_plan) is a function of (shape, widths, m, parity, dir, n_mom) and of the scratch it is given:
+// The launch plan (basis_slice_plan, slice_plan.hpp) is a function of (shape, widths, m, parity, dir, n_mom) and of the scratch it is given:
 //   pc     per form, the largest instantiated count <= max(n_mom, 1): momenta first, because a momentum taken in another
 //          launch costs a pass over V and b, a column taken in another launch a pass over b only
 //   group  MFMA: kb = 4 / (pc * (m / 16)) blocks; generic: cols = kBasisGenericCols.  Without momenta this is the largest
 //          group with pc = 1: V = 2 x 32 columns at m = 16 is one launch of 64 columns
 //   blocks one grid for every launch of the call, from the launch with the most entries per block, E = max pc * K_g * m:
 //          budget = min(2048, entries left of the scratch's half after the phase tables / E) -- 1024 blocks, or one fewer,
-//          at E = 1024 --; blocks per slice = budget / L_local, at most rows_of_a_slice / 64, at least 1
-//   chunk  rows per block = rows_of_a_slice / blocks per slice, rounded up to a multiple of 16; the blocks per slice are
-//          then recounted from the chunk.  A block never holds rows of two slices.
+//          at E = 1024 --; blocks per slice wanted = budget / L_local; the blocks per slice and the chunk follow from
+//          that as in every per-slice plan (slice_plan.hpp)
 //   shrink while the budget is below max(L_local, min(256, L_local * rows_of_a_slice / 64)) blocks -- one block per slice
 //          at the least, one per compute unit where the slices have the rows -- the form that holds E gives way: first its
 //          group (MFMA: one block fewer; generic: cols = half the group's columns, while it has a second field), then
@@ -40,42 +39,14 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <vector>
 
 #include "kernels.hpp"
 #include "kernels_basis.hpp"
+#include "slice_plan.hpp"
 
 namespace bcg {
 
-struct BasisSliceGroup {
-  bool mfma;
-  int first;   // MFMA: first 16-column block, counted over the blocks of all MFMA fields of V in order; generic: first field
-  int count;   // MFMA: blocks; generic: fields
-  int K, off;  // its columns off .. off + K - 1 of the basis
-};
-
-struct BasisSlicePlan {
-  int pc_mfma, kb;     // momenta per launch and blocks per group of the MFMA form
-  int pc_generic, cols;  // momenta per launch and the column bound of the generic form
-  int nbps;            // blocks per slice
-  int chunk;           // rows per block, a multiple of 16
-  int ltab;            // entries per phase table: the largest local extent among the directions != dir
-  int mu[3];           // the directions != dir in ascending order (table slots 0..2)
-  std::vector<BasisSliceGroup> groups;
-  int pc_of(const BasisSliceGroup& g) const { return g.mfma ? pc_mfma : pc_generic; }
-  int pc_max() const;  // over the groups
-};
-
-// widths[0 .. nv-1]: the widths of V; fast: the MFMA form is allowed (bcg_force_generic not set).  half_entries: the double2
-// the phase tables (table_entries) and the block partials may take.  Returns false when no plan fits: one block per slice
-// of (one block of 16 columns or one generic field, pc = 1) does not fit, or a slice has 2^30 rows or more.
-bool basis_slice_plan(const int* widths, int nv, int m, bool fast, const LatticeDev& lat, int parity, int dir, int n_mom,
-                      int64_t half_entries, BasisSlicePlan* plan);
-inline int64_t basis_slice_table_entries(const BasisSlicePlan& p) { return static_cast<int64_t>(p.pc_max()) * 3 * p.ltab; }
-// the smallest instantiated momentum count >= n (n <= the form's pc)
-int basis_slice_launch_pc(int n);
-
-// partials[((t * nbps + k) * pc + p) * K_g m + j * K_g + i], t < L_dir local, k < plan.nbps, p < pc
+// partials[((t * nbps + k) * pc + p) * K_g m + j * K_g + i], t < L_dir local, k < plan.walk.nbps, p < pc
 // tab: [pc][3][plan.ltab] phases of the LOCAL coordinates (device memory), or nullptr: no phase arithmetic (pc = 1)
 void launch_basis_slice_dot_mfma(hipStream_t s, int m, int kb, const LatticeDev& lat, int parity, int dir, const BasisSlicePlan& plan,
                                  int pc, const BasisBlocks& v, const double2* b, const double2* tab, double2* partials);

@@ -90,16 +90,15 @@ __global__ void __launch_bounds__(256) k_basis_slice_axpy_generic(int m, SGGeom 
   __shared__ double2 xs[RMAX * kBasisGenericCols];
   const int tid = threadIdx.x;
   const int Kg = v.K;
-  const int s = blockIdx.x / g.nbps, k = blockIdx.x - s * g.nbps;
+  const int s = blockIdx.x / g.nbps;
   const int t = list[2 * s];
   const double2* const Cs = C + static_cast<int64_t>(list[2 * s + 1]) * m * K;
   for (int e = tid; e < Kg * m; e += 256) {
     const int i = e / m, j = e - i * m;
     Ct[e] = Cs[static_cast<int64_t>(j) * K + off + i];
   }
-  const int teff = g.half0 ? t >> 1 : t;
-  const int r0 = k * g.chunk;
-  const int r1 = r0 + g.chunk < g.n_virtual ? r0 + g.chunk : g.n_virtual;
+  const SGBlock bk = sg_block(g, s, t);
+  const int teff = bk.teff, r0 = bk.r0, r1 = bk.r1;
   const int R = 256 / m < RMAX ? 256 / m : RMAX;
   const int rl = tid / m, j = tid - rl * m;
   const bool rd = beta != 0.0;
@@ -138,17 +137,14 @@ __global__ void __launch_bounds__(256) k_basis_slice_axpy_generic(int m, SGGeom 
 // the slices that are not listed: y <- beta y, or zeros; the elements of a chunk in row order, one per thread and step
 template <bool ZERO>
 __global__ void __launch_bounds__(256) k_slice_scale(int m, SGGeom g, const int* __restrict__ slices, double2* __restrict__ y, double beta) {
-  const int s = blockIdx.x / g.nbps, k = blockIdx.x - s * g.nbps;
-  const int t = slices[s];
-  const int teff = g.half0 ? t >> 1 : t;
-  const int r0 = k * g.chunk;
-  const int r1 = r0 + g.chunk < g.n_virtual ? r0 + g.chunk : g.n_virtual;
-  const int64_t n = static_cast<int64_t>(r1 - r0) * m;
+  const int s = blockIdx.x / g.nbps;
+  const SGBlock bk = sg_block(g, s, slices[s]);
+  const int64_t n = static_cast<int64_t>(bk.r1 - bk.r0) * m;
   for (int64_t x = threadIdx.x; x < n; x += 256) {
     const int rr = static_cast<int>(x / m), j = static_cast<int>(x - static_cast<int64_t>(rr) * m);
-    const int vr = r0 + rr;
+    const int vr = bk.r0 + rr;
     const int o = vr / g.run, e = vr - o * g.run;
-    const SGRow rw = sg_row<false>(g, t, teff, o, e, true);
+    const SGRow rw = sg_row<false>(g, bk.t, bk.teff, o, e, true);
     if (rw.ok) {
       double2* const p = y + rw.row * m + j;
       if (ZERO) {
@@ -188,49 +184,27 @@ void slice_axpy_mfma(hipStream_t s, int kb, unsigned blocks, const SGGeom& g, co
 
 }  // namespace
 
-bool basis_slice_axpy_plan(const LatticeDev& lat, int parity, int dir, int n_slices, BasisSliceAxpyPlan* plan) {
-  int n = 0;
-  plan->ltab = 1;
-  for (int mu = 0; mu < 4; ++mu)
-    if (mu != dir) {
-      plan->mu[n++] = mu;
-      if (lat.L[mu] > plan->ltab) plan->ltab = lat.L[mu];
-    }
-  int64_t n_virtual, run, inner;
-  slice_rows(lat, parity, dir, &n_virtual, &run, &inner);
-  if (n_virtual >= (int64_t(1) << 30)) return false;
-  const int64_t most = (n_virtual + 63) / 64;
-  int64_t nbps = kBasisSliceAxpyBlocks / (n_slices > 0 ? n_slices : 1);
-  if (nbps > most) nbps = most;
-  if (nbps < 1) nbps = 1;
-  const int64_t chunk = ((n_virtual + nbps - 1) / nbps + 15) / 16 * 16;
-  nbps = (n_virtual + chunk - 1) / chunk;
-  plan->nbps = static_cast<int>(nbps);
-  plan->chunk = static_cast<int>(chunk);
-  return true;
-}
-
 void launch_basis_slice_axpy_mfma(hipStream_t s, int m, int nblocks16, const LatticeDev& lat, int parity, int dir,
-                                  const BasisSliceAxpyPlan& plan, int n_slices, const int* list, double2* y, const BasisBlocks& v,
+                                  const SliceWalk& plan, int n_slices, const int* list, double2* y, const BasisBlocks& v,
                                   const double2* C, int K, int off, const double2* tab, double beta) {
-  const SGGeom g = slice_geom(lat, parity, dir, plan.chunk, plan.nbps, plan.ltab, plan.mu);
+  const SGGeom g = slice_geom(lat, parity, dir, plan);
   const unsigned blocks = static_cast<unsigned>(plan.nbps) * static_cast<unsigned>(n_slices);
   if (m == 16) slice_axpy_mfma<16>(s, nblocks16, blocks, g, list, y, v, C, K, off, tab, beta);
   else slice_axpy_mfma<32>(s, nblocks16, blocks, g, list, y, v, C, K, off, tab, beta);
 }
 
-void launch_basis_slice_axpy_generic(hipStream_t s, int m, const LatticeDev& lat, int parity, int dir, const BasisSliceAxpyPlan& plan,
+void launch_basis_slice_axpy_generic(hipStream_t s, int m, const LatticeDev& lat, int parity, int dir, const SliceWalk& plan,
                                      int n_slices, const int* list, double2* y, const BasisFields& v, const double2* C, int K, int off,
                                      const double2* tab, double beta) {
-  const SGGeom g = slice_geom(lat, parity, dir, plan.chunk, plan.nbps, plan.ltab, plan.mu);
+  const SGGeom g = slice_geom(lat, parity, dir, plan);
   const unsigned blocks = static_cast<unsigned>(plan.nbps) * static_cast<unsigned>(n_slices);
   if (tab) hipLaunchKernelGGL((k_basis_slice_axpy_generic<true>), dim3(blocks), dim3(256), 0, s, m, g, list, y, v, C, K, off, tab, beta);
   else hipLaunchKernelGGL((k_basis_slice_axpy_generic<false>), dim3(blocks), dim3(256), 0, s, m, g, list, y, v, C, K, off, tab, beta);
 }
 
-void launch_slice_scale(hipStream_t s, int m, const LatticeDev& lat, int parity, int dir, const BasisSliceAxpyPlan& plan, int n_slices,
+void launch_slice_scale(hipStream_t s, int m, const LatticeDev& lat, int parity, int dir, const SliceWalk& plan, int n_slices,
                         const int* slices, double2* y, double beta) {
-  const SGGeom g = slice_geom(lat, parity, dir, plan.chunk, plan.nbps, plan.ltab, plan.mu);
+  const SGGeom g = slice_geom(lat, parity, dir, plan);
   const unsigned blocks = static_cast<unsigned>(plan.nbps) * static_cast<unsigned>(n_slices);
   if (beta == 0.0) hipLaunchKernelGGL((k_slice_scale<true>), dim3(blocks), dim3(256), 0, s, m, g, slices, y, beta);
   else hipLaunchKernelGGL((k_slice_scale<false>), dim3(blocks), dim3(256), 0, s, m, g, slices, y, beta);

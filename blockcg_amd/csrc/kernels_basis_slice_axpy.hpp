@@ -5,7 +5,7 @@
 //   y_j(x, c) <- beta y_j(x, c)                                      on the sites of every other slice,
 //
 // V a list of fields whose widths sum to K, y of width m, C_s one K x m matrix per listed slice.  The rows of a slice are
-// walked as the per-slice Gram kernels walk them (slice_walk.hpp, described in kernels_slice_gram.hpp); the operands of a
+// walked as the per-slice Gram kernels walk them (slice_walk.hpp, described in slice_plan.hpp); the operands of a
 // launch are a GROUP of basis fields exactly as in bcg_basis_axpy (kernels_basis.hpp: basis_axpy_mfma_blocks blocks of 16
 // columns in the MFMA form, kBasisGenericFields fields and kBasisGenericCols columns in the generic one).  The first
 // group's launch carries beta, the later ones run at beta = 1.  A launch reads 48 (K_g + m) bytes per listed site and
@@ -24,11 +24,10 @@
 // The slices that are not listed are a second kernel on the same walk (k_slice_scale: y <- beta y, or zeros at beta == 0;
 // not launched at beta == 1), so that the listed-slice kernels carry no branch and no register for them.
 //
-// The launch plan (basis_slice_axpy_plan) is a function of (shape, parity, dir, number of slices of the launch) only --
-// widths and m choose the form and the groups, not the grid:
-//   blocks per slice = kBasisSliceAxpyBlocks / slices, at most rows_of_a_slice / 64, at least 1
-//   chunk            = rows_of_a_slice / blocks per slice, rounded up to a multiple of 16; the blocks per slice are then
-//                      recounted from the chunk.  A block never holds rows of two slices.
+// The launch plan (basis_slice_axpy_plan, slice_plan.hpp) is a function of (shape, parity, dir, number of slices of the
+// launch) only -- widths and m choose the form and the groups, not the grid -- and nothing but the walk (SliceWalk):
+//   blocks per slice wanted = kBasisSliceAxpyBlocks / slices; the blocks per slice and the chunk follow from that as in
+//   every per-slice plan (slice_plan.hpp)
 // The grid is slices x blocks per slice, so any number of slices is covered (one block per slice at the least); nothing is
 // reduced, so no value depends on the plan.  No plan: a slice of 2^30 rows or more.
 #pragma once
@@ -38,32 +37,21 @@
 
 #include "kernels.hpp"
 #include "kernels_basis.hpp"
+#include "slice_plan.hpp"
 
 namespace bcg {
-
-constexpr int kBasisSliceAxpyBlocks = 2048;  // the grid aimed at, as in the per-slice products
-
-struct BasisSliceAxpyPlan {
-  int nbps;   // blocks per slice
-  int chunk;  // rows per block, a multiple of 16
-  int ltab;   // entries per phase table: the largest local extent among the directions != dir
-  int mu[3];  // the directions != dir in ascending order (table slots 0..2)
-};
-
-// n_slices: the local slices the launch walks (>= 1).  Returns false when a slice has 2^30 rows or more.
-bool basis_slice_axpy_plan(const LatticeDev& lat, int parity, int dir, int n_slices, BasisSliceAxpyPlan* plan);
 
 // list[2 s] = local slice, list[2 s + 1] = index of its matrix in C, s < n_slices (device memory);
 // C[(index * m + j) * K + i] column-major K x m blocks; the group's columns are off .. off + K_g - 1.
 // tab: [3][plan.ltab] w of the LOCAL coordinates (device memory), or nullptr: no phase arithmetic.
 void launch_basis_slice_axpy_mfma(hipStream_t s, int m, int nblocks16, const LatticeDev& lat, int parity, int dir,
-                                  const BasisSliceAxpyPlan& plan, int n_slices, const int* list, double2* y, const BasisBlocks& v,
+                                  const SliceWalk& plan, int n_slices, const int* list, double2* y, const BasisBlocks& v,
                                   const double2* C, int K, int off, const double2* tab, double beta);
-void launch_basis_slice_axpy_generic(hipStream_t s, int m, const LatticeDev& lat, int parity, int dir, const BasisSliceAxpyPlan& plan,
+void launch_basis_slice_axpy_generic(hipStream_t s, int m, const LatticeDev& lat, int parity, int dir, const SliceWalk& plan,
                                      int n_slices, const int* list, double2* y, const BasisFields& v, const double2* C, int K, int off,
                                      const double2* tab, double beta);
 // y <- beta y (beta == 0: zeros, y is not read) on the slices slices[0 .. n_slices-1] (local, device memory)
-void launch_slice_scale(hipStream_t s, int m, const LatticeDev& lat, int parity, int dir, const BasisSliceAxpyPlan& plan, int n_slices,
+void launch_slice_scale(hipStream_t s, int m, const LatticeDev& lat, int parity, int dir, const SliceWalk& plan, int n_slices,
                         const int* slices, double2* y, double beta);
 
 }  // namespace bcg

@@ -8,29 +8,13 @@
 // coefficient matrix) are staged in LDS.
 #include <hip/hip_runtime.h>
 
+#include "complex_ops.hpp"
 #include "kernels.hpp"
 
 namespace bcg {
 
 namespace {
 
-__device__ __forceinline__ double2 cmul(double2 a, double2 b) {
-  return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-// acc += a*b
-__device__ __forceinline__ void cfma(double2& acc, double2 a, double2 b) {
-  acc.x = fma(a.x, b.x, acc.x);
-  acc.x = fma(-a.y, b.y, acc.x);
-  acc.y = fma(a.x, b.y, acc.y);
-  acc.y = fma(a.y, b.x, acc.y);
-}
-// acc += conj(a)*b
-__device__ __forceinline__ void cfma_conj(double2& acc, double2 a, double2 b) {
-  acc.x = fma(a.x, b.x, acc.x);
-  acc.x = fma(a.y, b.y, acc.x);
-  acc.y = fma(a.x, b.y, acc.y);
-  acc.y = fma(-a.y, b.x, acc.y);
-}
 // acc -= a*b
 __device__ __forceinline__ void cfms(double2& acc, double2 a, double2 b) {
   acc.x = fma(-a.x, b.x, acc.x);

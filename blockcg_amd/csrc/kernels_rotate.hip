@@ -2,19 +2,13 @@
 // in the operand ownership of Tile / rect_acc (kernels_basis.hip), restated here for a row stride of the whole K x K
 // matrix; four real products per complex one.  Generic form: lane = (row, output column) with the rows of a tile and Q in
 // LDS.  Plain stores, no atomics; 64-bit wherever an element offset is formed.
+#include "complex_ops.hpp"
 #include "kernels_rotate.hpp"
 #include "mfma_common.hpp"
 
 namespace bcg {
 
 namespace {
-
-__device__ __forceinline__ void cfma(double2& acc, double2 a, double2 b) {
-  acc.x = fma(a.x, b.x, acc.x);
-  acc.x = fma(-a.y, b.y, acc.x);
-  acc.y = fma(a.x, b.y, acc.y);
-  acc.y = fma(a.y, b.x, acc.y);
-}
 
 // rect_acc<16> of kernels_basis.hip for a matrix whose rows are LD doubles apart: A += in * C, C the 16 x 16 block at Ml
 // (Ml[j_in * LD + 2 j_out + comp]).  A.a[0] is the re block of the output tile, A.a[1] its im block.

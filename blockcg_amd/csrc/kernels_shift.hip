@@ -14,26 +14,12 @@
 // arguments): neither its links nor its neighbour rows are read.
 #include <hip/hip_runtime.h>
 
+#include "complex_ops.hpp"
 #include "kernels_shift.hpp"
 
 namespace bcg {
 
 namespace {
-
-// acc += a*b
-__device__ __forceinline__ void cfma(double2& acc, double2 a, double2 b) {
-  acc.x = fma(a.x, b.x, acc.x);
-  acc.x = fma(-a.y, b.y, acc.x);
-  acc.y = fma(a.x, b.y, acc.y);
-  acc.y = fma(a.y, b.x, acc.y);
-}
-// acc += conj(a)*b
-__device__ __forceinline__ void cfma_conj(double2& acc, double2 a, double2 b) {
-  acc.x = fma(a.x, b.x, acc.x);
-  acc.x = fma(a.y, b.y, acc.x);
-  acc.y = fma(a.x, b.y, acc.y);
-  acc.y = fma(-a.y, b.x, acc.y);
-}
 
 // acc += w * (U psi): u[k * 3 + r] = U(r, k), the links' column-major storage
 __device__ __forceinline__ void term_fwd(double2 acc[3], double2 w, const double2* u, const double2 psi[3]) {

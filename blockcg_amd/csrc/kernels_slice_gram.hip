@@ -1,5 +1,6 @@
 // Per-slice Gram matrices with momentum projection (gfx950): C_p(t) = sum_{x_dir = t} w_p(x) a(x)^dagger b(x), all column
-// pairs, PC momenta per pass over the operands.  The walk, the launch plan and the layouts: kernels_slice_gram.hpp.
+// pairs, PC momenta per pass over the operands.  The launch plan and the layouts: kernels_slice_gram.hpp; the walk:
+// slice_plan.hpp, slice_walk.hpp.
 // m = 16 and 32: v_mfma_f64_16x16x4_f64 through gram_step / GramAcc of mfma_common.hpp; every other width: one VALU
 // kernel with the rows of a chunk staged in LDS.  Plain stores, no atomics; 64-bit wherever an element offset is formed.
 #include "kernels_slice_gram.hpp"
@@ -9,13 +10,6 @@
 namespace bcg {
 
 namespace {
-
-__device__ __forceinline__ void cfma_conj(double2& acc, double2 a, double2 b) {
-  acc.x = fma(a.x, b.x, acc.x);
-  acc.x = fma(a.y, b.y, acc.x);
-  acc.y = fma(a.x, b.y, acc.y);
-  acc.y = fma(-a.y, b.x, acc.y);
-}
 
 // gram_block_store of mfma_common.hpp with the destination given: the per-wave fragments summed in wave order, one 16 x 16
 // block at a time through red (NW * 8 * 64 doubles), dst[j * M + i]
@@ -57,10 +51,9 @@ __global__ void __launch_bounds__(256) k_slice_gram_mfma(SGGeom g, const double2
   constexpr int NW = 4, JB = M / 16, U = M == 16 ? 4 : 2;
   __shared__ __attribute__((aligned(16))) double red[NW * 8 * 64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int t = blockIdx.x / g.nbps, k = blockIdx.x - t * g.nbps;
-  const int teff = g.half0 ? t >> 1 : t;
-  const int r0 = k * g.chunk;
-  const int r1 = r0 + g.chunk < g.n_virtual ? r0 + g.chunk : g.n_virtual;
+  const int t = blockIdx.x / g.nbps;
+  const SGBlock bk = sg_block(g, t, t);
+  const int teff = bk.teff, r0 = bk.r0, r1 = bk.r1;
   const int nq = (r1 - r0 + 3) >> 2;
   const int col = lane & 15;
   GramAcc<M> G[PC];
@@ -214,47 +207,10 @@ bool use_mfma(int m, bool mfma) { return mfma && (m == 16 || m == 32); }
 
 }  // namespace
 
-int slice_gram_launch_pc(int n) { return n <= 1 ? 1 : n <= 2 ? 2 : 4; }
-
-bool slice_gram_plan(int m, bool mfma, const LatticeDev& lat, int parity, int dir, int L_global, int n_mom, int64_t half_entries,
-                     SliceGramPlan* plan) {
-  const int64_t mm = static_cast<int64_t>(m) * m;
-  const int L = lat.L[dir];
-  int n = 0;
-  plan->ltab = 1;
-  for (int mu = 0; mu < 4; ++mu)
-    if (mu != dir) {
-      plan->mu[n++] = mu;
-      if (lat.L[mu] > plan->ltab) plan->ltab = lat.L[mu];
-    }
-  const int pc_max = use_mfma(m, mfma) && m == 16 ? 4 : 2;
-  int pc = 1;
-  while (2 * pc <= pc_max && 2 * pc <= n_mom && 2 * pc * L_global * mm <= half_entries) pc *= 2;
-  if (pc * L_global * mm > half_entries) return false;
-  plan->pc = pc;
-  int64_t n_virtual, run, inner;
-  slice_rows(lat, parity, dir, &n_virtual, &run, &inner);
-  if (n_virtual >= (int64_t(1) << 30)) return false;
-  const int64_t room = half_entries - slice_gram_table_entries(*plan);
-  if (room <= 0) return false;
-  int64_t budget = room / (pc * mm);
-  if (budget > 2048) budget = 2048;
-  int64_t nbps = budget / L;
-  const int64_t most = (n_virtual + 63) / 64;
-  if (nbps > most) nbps = most;
-  if (nbps < 1) nbps = 1;
-  const int64_t chunk = ((n_virtual + nbps - 1) / nbps + 15) / 16 * 16;
-  nbps = (n_virtual + chunk - 1) / chunk;
-  if (nbps * L > budget) return false;
-  plan->nbps = static_cast<int>(nbps);
-  plan->chunk = static_cast<int>(chunk);
-  return true;
-}
-
 void launch_slice_gram(hipStream_t s, int m, bool mfma, const LatticeDev& lat, int parity, int dir, const SliceGramPlan& plan, int pc,
                        const double2* a, const double2* b, const double2* tab, double2* partials) {
-  const SGGeom g = slice_geom(lat, parity, dir, plan.chunk, plan.nbps, plan.ltab, plan.mu);
-  const unsigned blocks = static_cast<unsigned>(plan.nbps) * static_cast<unsigned>(lat.L[dir]);
+  const SGGeom g = slice_geom(lat, parity, dir, plan.walk);
+  const unsigned blocks = static_cast<unsigned>(plan.walk.nbps) * static_cast<unsigned>(lat.L[dir]);
   if (use_mfma(m, mfma)) {
     if (m == 16) {
       if (!tab) launch_mfma<16, 1, false>(s, blocks, g, a, b, tab, partials);

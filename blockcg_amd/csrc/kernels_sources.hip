@@ -3,6 +3,7 @@
 // none uses the matrix pipe.  Element indices and byte offsets are 64-bit.
 #include <hip/hip_runtime.h>
 
+#include "complex_ops.hpp"
 #include "kernels_sources.hpp"
 
 namespace bcg {
@@ -142,13 +143,6 @@ struct SliceGeom {
   int L1, L2;         // half0: extents for the parity of o = x1 + L1 (x2 + L2 x3)
   int par_off;        // half0: field parity + parity of the local origin
 };
-
-__device__ __forceinline__ void cfma_conj(double2& acc, double2 a, double2 b) {
-  acc.x = fma(a.x, b.x, acc.x);
-  acc.x = fma(a.y, b.y, acc.x);
-  acc.y = fma(a.x, b.y, acc.y);
-  acc.y = fma(-a.y, b.x, acc.y);
-}
 
 struct SliceCursor {
   int64_t o, e, addr;

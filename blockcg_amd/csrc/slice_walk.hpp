@@ -1,13 +1,16 @@
-// The slice walk shared by the per-slice Gram kernels (kernels_slice_gram.hip) and the per-slice basis products
-// (kernels_basis_slice.hip): which rows of a field belong to slice t of a direction, in which order a block takes them, the
-// coordinates of a row's site and its momentum phase.  The walk itself is described in kernels_slice_gram.hpp.  Everything
-// lives in an anonymous namespace: each translation unit has its own copy, as with mfma_common.hpp.
+// The slice walk shared by the per-slice Gram kernels (kernels_slice_gram.hip), the per-slice basis products
+// (kernels_basis_slice.hip) and their adjoint (kernels_basis_slice_axpy.hip): which rows of a field belong to slice t of a
+// direction, in which order a block takes them, the coordinates of a row's site and its momentum phase.  The walk itself and
+// the plans that size it are described in slice_plan.hpp.  Everything lives in an anonymous namespace: each translation
+// unit has its own copy, as with mfma_common.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
+#include "complex_ops.hpp"
 #include "kernels.hpp"
+#include "slice_plan.hpp"
 
 namespace bcg {
 
@@ -33,6 +36,21 @@ struct SGRow {
   int x[3];     // local coordinates of its site along the three slots (0 where !ok)
 };
 
+// What a block walks: the virtual rows r0 .. r1 - 1 of slice t (teff: the slice in the row address)
+struct SGBlock {
+  int t, teff, r0, r1;
+};
+// the block's slice is the s-th of the grid (s = blockIdx.x / g.nbps) and slice t of the field
+__device__ __forceinline__ SGBlock sg_block(const SGGeom& g, int s, int t) {
+  SGBlock b;
+  const int k = blockIdx.x - s * g.nbps;
+  b.t = t;
+  b.teff = g.half0 ? t >> 1 : t;
+  b.r0 = k * g.chunk;
+  b.r1 = b.r0 + g.chunk < g.n_virtual ? b.r0 + g.chunk : g.n_virtual;
+  return b;
+}
+
 // virtual row v = o * run + e of slice t; live: v is inside the block's chunk
 template <bool COORDS>
 __device__ __forceinline__ SGRow sg_row(const SGGeom& g, int t, int teff, int o, int e, bool live) {
@@ -54,46 +72,38 @@ __device__ __forceinline__ SGRow sg_row(const SGGeom& g, int t, int teff, int o,
   return r;
 }
 
-__device__ __forceinline__ double2 cmul(double2 a, double2 b) {
-  return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
+// the staging loops' virtual row v of the block's slice: not live past the chunk's end, where (o, e) are those of row r0
+template <bool COORDS>
+__device__ __forceinline__ SGRow sg_row_at(const SGGeom& g, const SGBlock& b, int v) {
+  const bool live = v < b.r1;
+  const int vv = live ? v : b.r0;
+  const int o = vv / g.run, e = vv - o * g.run;
+  return sg_row<COORDS>(g, b.t, b.teff, o, e, live);
 }
+
 // w_p of a site: the three table entries multiplied in ascending direction
 __device__ __forceinline__ double2 sg_phase(const double2* __restrict__ tab, int ltab, int p, const int x[3]) {
   const double2* tp = tab + static_cast<int64_t>(p) * 3 * ltab;
   return cmul(cmul(tp[x[0]], tp[ltab + x[1]]), tp[2 * ltab + x[2]]);
 }
 
-// rows of one slice, rows and sites per run
-void slice_rows(const LatticeDev& lat, int parity, int dir, int64_t* n_virtual, int64_t* run, int64_t* inner) {
-  const int L = lat.L[dir];
-  if (parity >= 0 && dir == 0) {
-    *inner = 1;
-    *run = 3;
-    *n_virtual = lat.V / L * 3;  // every (x1, x2, x3); half of them hold x0 = t
-  } else {
-    *inner = parity >= 0 ? lat.stride[dir] / 2 : lat.stride[dir];  // half: x0 is compact
-    *run = *inner * 3;
-    *n_virtual = lat.V / (lat.stride[dir] * L) * *run;
-  }
-}
-
-// the kernels' view of a launch: mu the directions != dir in ascending order (table slots 0..2)
-SGGeom slice_geom(const LatticeDev& lat, int parity, int dir, int chunk, int nbps, int ltab, const int mu[3]) {
+// the kernels' view of a launch
+inline SGGeom slice_geom(const LatticeDev& lat, int parity, int dir, const SliceWalk& walk) {
   int64_t n_virtual, run, inner;
   slice_rows(lat, parity, dir, &n_virtual, &run, &inner);
   SGGeom g{};
   g.n_virtual = static_cast<int>(n_virtual);
   g.run = static_cast<int>(run);
   g.inner = static_cast<int>(inner);
-  g.chunk = chunk;
-  g.nbps = nbps;
+  g.chunk = walk.chunk;
+  g.nbps = walk.nbps;
   g.half0 = parity >= 0 && dir == 0;
   g.half = parity >= 0 && dir != 0;
   g.Leff = g.half0 ? lat.L[0] / 2 : lat.L[dir];
-  g.e0 = g.half ? lat.L[0] / 2 : lat.L[mu[0]];
-  g.e1 = lat.L[mu[1]];
+  g.e0 = g.half ? lat.L[0] / 2 : lat.L[walk.mu[0]];
+  g.e1 = lat.L[walk.mu[1]];
   g.par_off = parity >= 0 ? parity + ((lat.origin[0] + lat.origin[1] + lat.origin[2] + lat.origin[3]) & 1) : 0;
-  g.ltab = ltab;
+  g.ltab = walk.ltab;
   return g;
 }
 
