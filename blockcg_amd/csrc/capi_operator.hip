@@ -287,6 +287,7 @@ int hop(bcg_context* c, const bcg_gauge* g, bcg_field* out, const bcg_field* in,
       ProfScope ps(c, "halo_exchange_end");
       BCG_TRY(exchange_end(c));
     }
+    if (tb.boundary_n > 0) note_stencil_form(c, plb);  // (counted like every launched plan: the boundary list's row form)
     {
       ProfScope ps(c, "hop_boundary");
       if (tb.boundary_n > 0)

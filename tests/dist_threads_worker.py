@@ -8,7 +8,12 @@ over the stand-in of tests/cpp/mock_rccl.hpp) of its own.  The stand-in runs in 
 call returns when its bytes have arrived; blocking host functions of eight streams in one process could otherwise share
 one runtime callback thread) -- the asynchronous begin/end choreography is what the 2- and 4-process tests exercise; this
 one is about the message plan, the ghost layout and the ring windows of the headline's grid.  Every rank checks operator,
-Gram matrix and a fixed-work solve of its sub-lattice against the CPU oracle on the whole lattice."""
+Gram matrix and a fixed-work solve of its sub-lattice against the CPU oracle on the whole lattice.
+
+BCG_TEST_OVERLAP=0 (tests/test_distributed_default_tuning.py): the transport without its split callbacks, as
+tests/dist_gpu_worker.py attaches it -- every exchange blocks, the stencil runs as one whole launch (tile class 0) and a
+capacity ring takes its serial form (windows of ring - 2 slices).  BCG_TEST_JOIN_TIMEOUT: seconds the main thread waits
+for a rank (default 900).  The stencil_form_* counters on the DIST_THREADS_OK line cover operator and solve, rank by rank."""
 import os
 import sys
 import threading
@@ -30,6 +35,8 @@ def main():
     grid = [int(x) for x in os.environ["BCG_TEST_GRID"].split(",")]
     m = int(os.environ["BCG_TEST_M"])
     ring = int(os.environ.get("BCG_TEST_RING", "0"))
+    split_exchange = os.environ.get("BCG_TEST_OVERLAP", "1") != "0"
+    join_timeout = float(os.environ.get("BCG_TEST_JOIN_TIMEOUT", "900"))
     assert os.environ.get("BCG_MOCK_SYNC") == "1" and "mock" in os.path.basename(rccl.LIB_PATH)
     world = int(np.prod(grid))
     mass, shifts, iters = 0.1, [0.0, 1e-3, 1e-1], 4
@@ -59,14 +66,17 @@ def main():
             ctx = bc.Context(gdims, device=0, grid=grid, coords=coords)
             comm = rccl.RcclComm(ctx, uid, rank, world)
             assert comm.communicators == 2
+            if not split_exchange:  # blocking exchange only: drop the split callbacks (as dist_gpu_worker.py does)
+                from blockcg_amd import _lib
+                cb = comm.callbacks
+                ctx.set_comm(_lib.bcg_comm(cb.user, cb.halo_exchange, cb.allreduce_sum, _lib.HALO_CB(), _lib.HALO_END_CB()), comm)
             ctx.capacity_mode(ring)
             D = bc.dirac_op(ctx, mass, seed=3)
             B = bc.block_fermion_field(ctx, m).setRandom(seed=4)
             out = bc.block_fermion_field(ctx, m)
             ctx.profiling(True)
             D.op(out, B)
-            prof = ctx.profile()
-            ctx.profiling(False)
+            prof = ctx.profile()  # (of the operator alone; the counters run on through the solve)
             L, og = ctx.local_dims, ctx.origin
             sl = tuple(slice(a, a + b) for a, b in zip(og, L))[::-1]
 
@@ -76,7 +86,12 @@ def main():
             assert np.array_equal(B.download(), local(Bh))
             e_op = rel(out.download(), local(want_op))
             assert e_op < 2e-13, ("op", rank, e_op)
-            if ring:
+            if ring and not split_exchange:
+                # serial form: the source's faces whole, the tmp faces chunk by chunk, the source's faces of slice 0 once more
+                chunks = (L[3] + ring - 3) // (ring - 2)
+                assert prof["halo_exchange"]["count"] == chunks + 2 and "halo_exchange_begin" not in prof, prof
+                assert "hop_ring" in prof, sorted(prof)
+            elif ring:
                 C = (ring - 2) // 2
                 chunks = (L[3] + C - 1) // C
                 # the source's faces in two windows (the slices the first launches read, then the rest), the tmp faces per chunk:
@@ -92,6 +107,8 @@ def main():
             for s in range(len(shifts)):
                 e = rel(X[s].download(), local(o["X"][s]))
                 assert e < 1e-11, ("X", s, rank, e)
+            prof = ctx.profile()
+            ctx.profiling(False)
             if half:
                 half_volume_checks(ctx, comm, orc, D, B, U, Bh, gdims, mass, m, local, rel, pre=half_pre)
             notes[rank] = (e_op, {k[len("stencil_form_"):]: v["count"] for k, v in prof.items() if k.startswith("stencil_form_")})
@@ -106,7 +123,7 @@ def main():
     for t in threads:
         t.start()
     for t in threads:
-        t.join(timeout=900)
+        t.join(timeout=join_timeout)
     hung = [t.name for t in threads if t.is_alive()]
     bad = [(r, e) for r, e in enumerate(errors) if e]
     if hung or bad:
@@ -114,7 +131,8 @@ def main():
             print(f"--- rank {r} ---\n{e}", file=sys.stderr)
         print("hung:", hung, file=sys.stderr, flush=True)
         os._exit(1)
-    print("DIST_THREADS_OK", world, grid, "ring", ring, "op err %.2e" % max(n[0] for n in notes), notes[0][1])
+    print("DIST_THREADS_OK", world, grid, "ring", ring, "op err %.2e" % max(n[0] for n in notes), notes[0][1],
+          "forms", " ".join(f"rank{r}:" + ",".join(f"{k}={v}" for k, v in sorted(n[1].items())) for r, n in enumerate(notes)))
 
 
 if __name__ == "__main__":
