@@ -142,6 +142,12 @@ SIGNATURES = {
                                         ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                         ctypes.c_double, ctypes.c_double, ctypes.c_int, c_dbl_p, c_dbl_p, c_int_p,
                                         ctypes.POINTER(ctypes.c_int64)]),
+    "bcg_basis_slice_rotate": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int, ctypes.c_int, c_int_p,
+                                              c_dbl_p]),
+    "bcg_laplacian_modes": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
+                                           ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_double, ctypes.c_double, ctypes.c_int, c_dbl_p, c_dbl_p, c_int_p,
+                                           ctypes.POINTER(ctypes.c_int64)]),
 }
 
 _lib = None

@@ -676,6 +676,57 @@ def lowest_modes(V, D, n_want, upper_bound, degree=16, tol=1e-10, max_iterations
     return dict(evals=evals, resid=resid, iterations=it.value, applications=apps.value)
 
 
+def basis_slice_rotate(V, Q, dir, slices=None):
+    """V(x) <- V(x) Q[s] in place on the sites with global x_dir = slices[s] (bcg_basis_slice_rotate): basis_rotate with one
+    matrix per slice.  Q: an (S, K, K) array, one matrix per listed slice, none of them need be unitary; slices: a list of
+    distinct global slice indices (None: all L_dir slices in ascending order).  The sites of the other slices are neither read
+    nor written.  Purely local; no second copy of the basis."""
+    Vh, nv, K = _basis_handles(V)
+    ctx = V[0].ctx
+    if not 0 <= int(dir) < ctx.ndim:
+        raise BlockCGError(1, "basis_slice_rotate: direction outside the lattice")
+    if slices is None:
+        S, sl, n_slices = ctx.dims[int(dir)], None, 0
+    else:
+        arr = np.ascontiguousarray(list(slices), dtype=np.intc)
+        if arr.ndim != 1 or arr.size == 0:
+            raise BlockCGError(1, "basis_slice_rotate: slices is a non-empty list of slice indices")
+        S, sl, n_slices = int(arr.size), arr.ctypes.data_as(_lib.c_int_p), int(arr.size)
+    Q = np.asarray(Q, dtype=np.complex128)
+    if Q.shape != (S, K, K):
+        raise ValueError(f"expected {S} matrices of {K}x{K}")
+    Qt = np.ascontiguousarray(Q.transpose(0, 2, 1))  # column-major blocks
+    ctx.check(ctx.lib.bcg_basis_slice_rotate(Vh, nv, int(dir), n_slices, sl, _dp(Qt)))
+    return V
+
+
+def laplacian_modes(V, links, dir, n_want, upper_bound, degree=16, tol=1e-10, max_iterations=100, locked=None):
+    """The lowest eigenpairs of -Lap_dir (the covariant Laplacian without direction dir, laplacian(..., dir) negated) on every
+    slice of dir at once (bcg_laplacian_modes): a distillation basis.  links: a dirac_op or a gauge_field.  V: the start block
+    (a list of full fields, K <= 64 columns in all, filled by the caller); on return V is orthonormal on every slice with
+    ascending Ritz values per slice.  locked: vectors orthonormal per slice that V is kept orthogonal to, slice by slice.
+    upper_bound: of the spectrum; 4 (ndim - 1) for unitary links.  n_want, degree, tol, max_iterations and the guard block of
+    n_want == K as in lowest_modes; converged when every slice is.  Returns a dict: evals and resid ([L_dir, K] each),
+    iterations (filter applications), applications (shift_sum calls)."""
+    Vh, nv, K = _basis_handles(V)
+    ctx = links.ctx
+    if locked:
+        Lh, nl, _ = _basis_handles(locked)
+    else:
+        Lh, nl = None, 0
+    if not 0 <= int(dir) < ctx.ndim:
+        raise BlockCGError(1, "laplacian_modes: direction outside the lattice")
+    L = ctx.dims[int(dir)]
+    evals = np.zeros((L, K))
+    resid = np.zeros((L, K))
+    it = ctypes.c_int()
+    apps = ctypes.c_int64()
+    ctx.check(ctx.lib.bcg_laplacian_modes(ctx.h, links.h, int(dir), Vh, nv, Lh, nl, int(n_want), int(degree), float(upper_bound),
+                                          float(tol), int(max_iterations), _dp(evals), _dp(resid), ctypes.byref(it),
+                                          ctypes.byref(apps)))
+    return dict(evals=evals, resid=resid, iterations=it.value, applications=apps.value)
+
+
 def _trace_buffers(trace_limit, S, m):
     if trace_limit <= 0:
         return None, None, None

@@ -6,8 +6,9 @@
 //   capi_sources.hip    noise fields, point / wall sources, the slice-resolved inner product
 //   capi_shift.hip      the covariant nearest-neighbour sum with free coefficients, covariant smearing
 //   capi_basis.hip      products between fields of unequal width (V^dagger b, y <- beta y + V C, V^dagger b by slice), the column copy
-//   capi_rotate.hip     V <- V Q in place for a whole basis of at most 64 columns
-//   capi_lowmodes.hip   the low-mode eigensolver: Lanczos bound, Chebyshev-filtered subspace iteration (host composition)
+//   capi_rotate.hip     V <- V Q in place for a whole basis of at most 64 columns, and with one Q per slice on listed slices
+//   capi_lowmodes.hip   the low-mode eigensolver: Lanczos bound, Chebyshev-filtered subspace iteration (host composition),
+//                       and the same iteration slice by slice for the Laplacian modes of a distillation basis
 //   capi_slice.hpp      what the per-slice calls share: direction and momentum checks, phase tables (capi_sources, capi_basis)
 // Host code only; every loop over lattice sites is a HIP kernel (kernels_generic.hip, kernels_mfma.hip, kernels_stencil.hip).
 #pragma once

@@ -98,6 +98,7 @@ struct bcg_context {
   hipEvent_t basis_uploaded = nullptr;   // the last upload from pin_basis has left the host buffer
   double2* dev_rotate = nullptr;         // K x K matrix of bcg_basis_rotate, K <= 64 (capi_rotate.hip); allocated on first use
   double* pin_rotate = nullptr;          // pinned host copy
+  size_t rotate_entries = 0;             // double2 in either: 64 x 64, grown by bcg_basis_slice_rotate (one matrix per slice)
   hipEvent_t rotate_uploaded = nullptr;  // the last upload from pin_rotate has left the host buffer
   double2* staging = nullptr;            // layout-conversion staging of bcg_field_download_sites
   size_t staging_bytes = 0;

@@ -80,7 +80,8 @@ bool basis_slice_plan(const int* widths, int nv, int m, bool fast, const Lattice
                       int64_t half_entries, BasisSlicePlan* plan);
 inline int64_t basis_slice_table_entries(const BasisSlicePlan& p) { return static_cast<int64_t>(p.pc_max()) * 3 * p.walk.ltab; }
 
-// ---- bcg_basis_slice_axpy (kernels_basis_slice_axpy.hpp): its plan is the walk and nothing else ------
+// ---- bcg_basis_slice_axpy (kernels_basis_slice_axpy.hpp) and bcg_basis_slice_rotate (kernels_basis_slice_rotate.hpp):
+// ---- their plan is the walk and nothing else ----------------------------------------------------------
 constexpr int kBasisSliceAxpyBlocks = 2048;  // the grid aimed at, as in the per-slice products
 
 // n_slices: the local slices the launch walks (>= 1).  Returns false when a slice has 2^30 rows or more.

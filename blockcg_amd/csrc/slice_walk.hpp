@@ -1,5 +1,6 @@
 // The slice walk shared by the per-slice Gram kernels (kernels_slice_gram.hip), the per-slice basis products
-// (kernels_basis_slice.hip) and their adjoint (kernels_basis_slice_axpy.hip): which rows of a field belong to slice t of a
+// (kernels_basis_slice.hip), their adjoint (kernels_basis_slice_axpy.hip) and the rotation by slice
+// (kernels_basis_slice_rotate.hip): which rows of a field belong to slice t of a
 // direction, in which order a block takes them, the coordinates of a row's site and its momentum phase.  The walk itself and
 // the plans that size it are described in slice_plan.hpp.  Everything lives in an anonymous namespace: each translation
 // unit has its own copy, as with mfma_common.hpp.

@@ -536,6 +536,55 @@ int bcg_lowest_modes(bcg_context* ctx, const bcg_gauge* g, double mass, bcg_fiel
                      int max_iterations, double* evals_out, double* resid_out, int* iterations_out,
                      int64_t* applications_out);
 
+/* ---- the distillation basis: per-slice rotation and Laplacian modes (extensions) -----------------
+ * bcg_basis_slice_rotate: V(x) <- V(x) Q_s in place on the sites with GLOBAL x_dir = slices[s]: bcg_basis_rotate with one
+ * matrix per slice.  V as in bcg_basis_rotate (one context, parity and site count, widths 1 .. 32, no field twice, K <=
+ * BCG_BASIS_ROTATE_MAX_COLUMNS); dir, n_slices and slices as in bcg_basis_slice_axpy (distinct global indices in any order;
+ * n_slices = 0 with slices = NULL: all L_dir slices ascending).  Q[(s*K + j)*K + i], interleaved (re, im): one column-major
+ * K x K matrix per listed slice; the matrices need not be unitary.  Sites of slices that are not listed are neither read
+ * nor written; a half field along direction 0 skips the other parity's sites.  Full and half fields, divided lattices.
+ * Purely local: no bcg_comm call, and a rank that holds none of the listed slices launches nothing.  One launch takes all K
+ * columns of the listed local slices on the walk of bcg_basis_slice_axpy; every width in {16, 32} takes the MFMA form, every
+ * other width list and bcg_force_generic the generic one.  No atomics and nothing reduced: the same bits on every call.
+ * Where Q_s is a permutation matrix or the identity, the columns of that slice move bit for bit.  Does not synchronize the
+ * stream (unless the matrix buffer has to grow).  The matrices of the local listed slices and the slice list go through the
+ * buffer of bcg_basis_rotate, grown when a call needs more and freed by bcg_context_destroy.
+ *  - Profile keys "basis_slice_rotate" (96 K bytes per listed site, 8 K^2 flops per row), "basis_slice_rotate_mfma" /
+ *    "basis_slice_rotate_generic" (launch counts).
+ *  - BCG_ERR_INVALID: everything bcg_basis_rotate rejects (a NULL pointer, nv < 1, a field twice, mixed contexts, parities or
+ *    site counts, a non-finite Q), dir outside 0 .. ndim-1, n_slices < 0, n_slices > 0 with slices == NULL, a slice outside
+ *    0 .. L_dir-1 or listed twice.  BCG_ERR_UNSUPPORTED: K > 64, or a slice of 2^30 rows or more.  All are returned before
+ *    the first launch and leave V exactly as it was.
+ *
+ * bcg_laplacian_modes: the lowest eigenpairs of A = -Lap_dir on every slice of direction dir at once,
+ *   A psi(x) = 2 (ndim-1) psi(x) - sum_{mu != dir} [U_mu(x) psi(x+mu) + U_mu(x-mu)^dagger psi(x-mu)],
+ * bcg_dirac_shift_sum with a zero coefficient along dir (the links of direction dir are not read).  A is Hermitian for any
+ * links and block-diagonal over the slices of dir, so every slice has its own eigenproblem; the call is bcg_lowest_modes
+ * slice by slice: per-slice Gram and projected matrices (bcg_basis_slice_dot), per-slice Cholesky and Ritz rotations
+ * (two bcg_basis_slice_rotate calls over all slices per outer iteration), per-slice residuals (bcg_field_slice_dot).
+ *   V, locked, n_want, degree, tol, max_iterations, the guard block (n_want == K: min(16, 64 - K) columns of fixed-seed
+ *               noise by global site) and the counting: as in bcg_lowest_modes.  locked: orthonormal PER SLICE, any total width.
+ *   upper_bound of the spectrum of A, from the caller: 4 (ndim-1) bounds it for unitary links; general (e.g. smeared,
+ *               unprojected) links need a bound of the caller's own.
+ *   evals_out, resid_out   L_dir x K each ([t*K + i], t the GLOBAL slice): Ritz values ascending per slice, and
+ *               ||A v_i - theta_i(t) v_i|| over the sites of slice t.
+ *   iterations_out, applications_out   filter applications; bcg_dirac_shift_sum calls, nf (2 (iterations + 1) + degree
+ *               iterations), nf = nv, or nv + 1 with the guard block.  Either may be NULL.
+ * Converged when the maximum over all slices and the first n_want columns of resid is <= tol * upper_bound.  The filter is
+ * ONE Chebyshev polynomial for all slices, damping [max_t theta_last(t), upper_bound] and scaled at min_t theta_1(t), so its
+ * coefficients are global and a step is one bcg_dirac_shift_sum plus one axpby.  Reaching max_iterations is no error.
+ * Allocates and frees three work fields of the widest width.  Every branch is taken on all-reduced data: every rank of a
+ * divided lattice, divided along dir or not, returns the same status.
+ * BCG_ERR_INVALID: everything bcg_lowest_modes rejects, and dir outside 0 .. ndim-1.  BCG_ERR_UNSUPPORTED: K > 64; half
+ * fields (one hop flips the parity, as in bcg_covariant_smear).  Both before anything is launched.  BCG_ERR_NUMERIC: on any
+ * slice, V(t)^dagger V(t) not positive definite, a Ritz value at or above upper_bound, or Ritz values that do not spread;
+ * V, evals_out and resid_out then as bcg_lowest_modes leaves them. */
+int bcg_basis_slice_rotate(bcg_field* const* V, int nv, int dir, int n_slices, const int* slices, const double* Q);
+int bcg_laplacian_modes(bcg_context* ctx, const bcg_gauge* g, int dir, bcg_field* const* V, int nv,
+                        const bcg_field* const* locked, int nlocked, int n_want, int degree, double upper_bound,
+                        double tol, int max_iterations, double* evals_out /* L_dir x K */,
+                        double* resid_out /* L_dir x K */, int* iterations_out, int64_t* applications_out);
+
 #ifdef __cplusplus
 }
 #endif
