@@ -78,7 +78,8 @@ def main():
 
     residues = [0.9, -1.1, 0.4]  # three shifts with two work fields: launches of two and one
     worst = 0.0
-    for parity in (None, 0, 1):
+    # half fields need every local extent even (the library refuses them otherwise): full fields only at an odd one
+    for parity in (None, 0, 1) if all(n % 2 == 0 for n in L) else (None,):
         got = forces(ctx, m, parity, residues)
         if comm.error:
             raise comm.error

@@ -17,8 +17,11 @@ from blockcg_amd.comm import TorchDistComm, coords_of  # noqa: E402
 def fields(ctx, m, parity, pts, col, sl):
     """The fields under test on this context: three kinds of noise, point sources, walls along 0 and 3."""
     new = lambda: bc.block_fermion_field(ctx, m, parity=parity)  # noqa: E731
-    return [new().setGaussian(5), new().setZ2(6), new().setZ4(7), new().setPointSources(pts, col),
-            new().setWallSources(0, sl[0], col, -1), new().setWallSources(3, sl[3], col, -1 if parity is None else parity)]
+    f = [new().setGaussian(5), new().setZ2(6), new().setZ4(7), new().setPointSources(pts, col),
+         new().setWallSources(0, sl[0], col, -1), new().setWallSources(3, sl[3], col, -1 if parity is None else parity)]
+    if parity is None:  # the parity filter on a full field: the walls' even and odd sites by their GLOBAL coordinates
+        f += [new().setWallSources(mu, sl[mu], col, par) for mu in (0, 3) for par in (0, 1)]
+    return f
 
 
 def main():
@@ -36,9 +39,11 @@ def main():
         ctx = bc.Context(gdims, device=0, grid=grid, coords=coords_of(rank, grid), stream=comm.stream_ptr)
         comm.attach(ctx)
         sl = tuple(slice(o, o + n) for o, n in zip(ctx.origin, ctx.local_dims))[::-1]
+        # half fields need every local extent even (the library refuses them otherwise): full fields only at an odd one
+        parities = (None, 0, 1) if all(n % 2 == 0 for n in ctx.local_dims) else (None,)
         for m in widths:
             rng = np.random.default_rng(100 + m)  # the same draws on every rank
-            for parity in (None, 0, 1):
+            for parity in parities:
                 pts = [[int(rng.integers(0, d)) for d in gdims] for _ in range(m)]
                 if parity is not None:
                     for p in pts:
