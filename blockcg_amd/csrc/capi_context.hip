@@ -391,6 +391,7 @@ int bcg_context_create(bcg_context** out, int device, void* stream, int ndim, co
   if (const char* e = std::getenv("BCG_ROW_BLOCKS_C")) c->row_blocks_C = std::atoi(e);
   if (const char* e = std::getenv("BCG_ROW_BATCHED")) c->row_batched = std::atoi(e) != 0;
   if (const char* e = std::getenv("BCG_HOP_FACTORED")) c->hop_factored = std::atoi(e) != 0;
+  if (const char* e = std::getenv("BCG_HOP_FUSED_B")) c->hop_fused_b = std::atoi(e) != 0;
   if (const char* e = std::getenv("BCG_HOP_WALK")) c->hop_tune.patch_walk = std::atoi(e) != 0;
   if (const char* e = std::getenv("BCG_HOP_BLOCKS")) c->hop_tune.blocks = std::atoi(e);
   if (const char* e = std::getenv("BCG_HOP_BLOCKS_OVERLAP")) c->hop_tune.blocks_overlap = std::atoi(e);

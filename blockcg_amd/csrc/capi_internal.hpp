@@ -196,6 +196,16 @@ int reserve_operator_scratch(bcg_context* c, const bcg_field* like);
 // phase_A (capi_solvers.hip) is its only consumer
 int apply_shifted(bcg_context* c, const bcg_gauge* g, double mass, double sigma0, bcg_field* T, const bcg_field* P,
                   int* gram_blocks = nullptr, bool* gram_folded = nullptr, bool* gram_self = nullptr);
+// The factored pair with phase B of SBCGrQ inside the second factor (BCG_HOP_FUSED_B): the plans of both launches, made
+// before the first runs.  fused_pair: false where the path is not taken (the callers then run apply_shifted and phase B).
+struct FusedPair {
+  bcg::HopLaunchPlan f1, f2;
+  double mu = 0.0;  // sqrt(mass^2 + sigma0)
+};
+bool fused_pair(const bcg_context* c, int m, double mass, double sigma0, FusedPair& fp);
+int fused_first_factor(bcg_context* c, const bcg_gauge* g, const FusedPair& fp, const bcg_field* P, int* gram_blocks, bool* gram_folded);
+int fused_second_factor(bcg_context* c, const bcg_gauge* g, const FusedPair& fp, const bcg_field* Q, bcg_field* Qout,
+                        const double2* mats, bool has_rinv, int* gram_blocks, bool* gram_folded);
 
 // ---- capi_solvers.hip ------------------------------------------------------------------------------
 // Phase A of an iteration: T = (A + sigma0) P ; G = P^dagger T   (:134-140)

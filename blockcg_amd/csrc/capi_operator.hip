@@ -676,6 +676,64 @@ int apply_shifted(bcg_context* c, const bcg_gauge* g, double mass, double sigma0
   return hop(c, g, T, tmp, bcg::HOP_SHIFTED, P, mass * mass + sigma0, gram_blocks, gram_folded);
 }
 
+// ---- the factored pair with phase B of SBCGrQ inside the second factor (BCG_HOP_FUSED_B, default on) ----
+// G = P^dagger T = W^dagger W needs no T: the first factor sums it from its own output (HOP_FACT1G), so alpha = G^-1 is on
+// the host before the second factor starts, and that launch (HOP_FACT2B) applies phase B's update to each site's T while it is
+// on chip: Q' = Q rho_prev^-1 - T alpha with the partials of Q'^dagger Q'.  T is neither written nor read -- 2 s of the 3 s
+// phase B moved -- and the phase B launch is gone.  Taken where factored_pair is, if both plans are bundle plans (both are made
+// before the first launch); everything else keeps apply_shifted and the phase B kernels.
+bool fused_pair(const bcg_context* c, int m, double mass, double sigma0, FusedPair& fp) {
+  const double c0 = mass * mass + sigma0;
+  if (!c->hop_fused_b || !c->hop_factored || m != 16 || !(c0 > 0.0) || c->distributed || c->force_tile_classes || !fast_hop(c, m) ||
+      !fast_rows(c, m) || capacity_path(c, m))
+    return false;
+  fp.f1 = plan_stencil(c, c->lat, c->hop_tune, {m, bcg::HOP_FACT1G, true, 0, bcg::HopWindow(), true});
+  fp.f2 = plan_stencil(c, c->lat, c->hop_tune, {m, bcg::HOP_FACT2B, true, 0, bcg::HopWindow(), true});
+  fp.mu = std::sqrt(c0);  // (as in apply_shifted)
+  return fp.f1.form == bcg::HOP_FORM_BUNDLE && fp.f2.form == bcg::HOP_FORM_BUNDLE;
+}
+// W = (mu - D) P into the operator's tmp, with the partials of W^dagger W
+int fused_first_factor(bcg_context* c, const bcg_gauge* g, const FusedPair& fp, const bcg_field* P, int* gram_blocks, bool* gram_folded) {
+  bcg_field* tmp;
+  BCG_TRY(get_tmp(c, P->m, &tmp));
+  BCG_TRY(halo_gauge(c, const_cast<bcg_gauge*>(g)));
+  if (c->profiling) c->prof["stencil_form_factored_pair"].count += 1;
+  note_stencil_form(c, fp.f1);
+  {
+    ProfScope ps(c, "hop", alg_bytes(c, P->m, 2, 1), hop_flops(c, P->m, true));
+    *gram_blocks = bcg::hop_launch(c->stream, fp.f1, g->U, g->Ughost, P->d, c->halo_recv, tmp->d, nullptr, fp.mu, c->partials);
+  }
+  *gram_folded = fp.f1.fold.out != nullptr;
+  return check_launch(c, "hop");
+}
+// Qout = Q [rho_prev^-1] - ((mu + D) W) alpha with the partials of Qout^dagger Qout; mats = [-alpha][rho_prev^-1] on the
+// device.  Qout may be Q: a wave has read its rows of Q when it writes them, and no other wave touches them.
+// Booking: existing tests pin the classes -- with the factored pair on, hop_shifted_gram has hop's count and hop's bytes, and
+// phaseB is counted once per iteration.  So the launch goes under hop_shifted_gram with its time, the stencil's streams
+// (2 s + g) and the stencil's and the Gram product's flops; phase B's share -- Q read and Q' written, 2 s, and its products --
+// under phaseB with count 1 and NO time (bench.py prices only classes that have time); stencil_form_fused_phaseB counts the
+// launches.
+int fused_second_factor(bcg_context* c, const bcg_gauge* g, const FusedPair& fp, const bcg_field* Q, bcg_field* Qout,
+                        const double2* mats, bool has_rinv, int* gram_blocks, bool* gram_folded) {
+  bcg_field* tmp;
+  BCG_TRY(get_tmp(c, Q->m, &tmp));
+  note_stencil_form(c, fp.f2);
+  if (c->profiling) {
+    c->prof["stencil_form_fused_phaseB"].count += 1;
+    bcg::ProfEntry& b = c->prof["phaseB"];
+    b.count += 1;
+    b.bytes += row_bytes(Q, 2);
+    b.flops += product_flops(Q, has_rinv ? 2 : 1);
+  }
+  {
+    ProfScope ps(c, "hop_shifted_gram", alg_bytes(c, Q->m, 2, 1), hop_flops(c, Q->m, true));
+    *gram_blocks = bcg::hop_launch(c->stream, fp.f2, g->U, g->Ughost, tmp->d, c->halo_recv, Qout->d, Q->d, fp.mu, c->partials, mats,
+                                   has_rinv ? 1 : 0);
+  }
+  *gram_folded = fp.f2.fold.out != nullptr;
+  return check_launch(c, "hop_shifted_gram");
+}
+
 }  // namespace bcg_impl
 
 using namespace bcg_impl;

@@ -66,6 +66,38 @@ int phase_B(bcg_context* c, bcg_field* Q, const bcg_field* T, const CMat& alpha,
   return finish_gram(c, m, nb, G2, true, /*folded=*/true);
 }
 
+// Phases A and B on the factored pair with phase B inside the second factor (capi_operator.hip: fused_pair).  The order of an
+// iteration becomes: first factor, reduction #1, the inversion, the uploads of -alpha and rho_prev^-1, the fused launch,
+// reduction #2.  T is not written; the caller's T field stays allocated and keeps its place in the rotation of residual buffers.
+bool plan_fused_pair(bcg_context* c, const bcg_field* P, double mass, double sigma0, FusedPair& fp) {
+  const int m = P->m;
+  if (!c->hop_fused_b || m != 16 || P->parity >= 0 || !fast_hop(c, m)) return false;  // (half fields keep their kernels)
+  if (ensure_scratch(c) != BCG_OK) return false;
+  return fused_pair(c, m, mass, sigma0, fp);
+}
+int phase_A_fused(bcg_context* c, const bcg_gauge* g, const FusedPair& fp, const bcg_field* P, CMat& G) {
+  int nb = 0;
+  bool folded = false;
+  BCG_TRY(fused_first_factor(c, g, fp, P, &nb, &folded));
+  BCG_TRY(finish_gram(c, P->m, nb, G, true, folded));
+  c->phaseA_gram_raw = CMat(P->m, c->pin_gram);
+  for (int i = 0; i < P->m; ++i) G(i, i) = G(i, i).real();  // (exactly real already: gram_self_block_store; as in phase_A)
+  c->phaseA_gram = G;
+  return BCG_OK;
+}
+int phase_B_fused(bcg_context* c, const bcg_gauge* g, const FusedPair& fp, bcg_field* Q, const CMat& alpha, CMat& G2,
+                  const CMat* rinv_prev, bcg_field* Qout) {
+  const int m = Q->m;
+  const CMat na = -alpha;
+  const CMat* two[2] = {&na, rinv_prev};
+  const double2* Md;
+  BCG_TRY(upload_mats(c, m, two, rinv_prev ? 2 : 1, &Md));
+  int nb = 0;
+  bool folded = false;
+  BCG_TRY(fused_second_factor(c, g, fp, Q, Qout ? Qout : Q, Md, rinv_prev != nullptr, &nb, &folded));
+  return finish_gram(c, m, nb, G2, true, folded);
+}
+
 // Phase C: Q <- Q rho^{-1} ; X_s += P_s A_s ; P_s <- P_s B_s + Q for the n active shifts
 // (:152 second half, :145, :158, :175, :177)
 int trisolve(bcg_context* c, bcg_field* y, const CMat& R);
@@ -630,7 +662,10 @@ int sbcgrq_iteration(bcg_sbcgrq_state* st, bcg_sbcgrq_trace* trace, bool more_fo
   // T = (A + sigma_0) P_0 ; alpha_inv = P_0^dagger T                          :134-140
   ++st->iter;                                            // :137
   st->alpha_inv_old = st->alpha_inv;                     // :139
-  BCG_TRY(phase_A(c, st->g, st->mass, sigma[0], st->T, st->P[0], st->alpha_inv));  // global reduction #1
+  FusedPair fp;  // (both launches planned here, before the first)
+  const bool fused = plan_fused_pair(c, st->P[0], st->mass, sigma[0], fp);
+  if (fused) BCG_TRY(phase_A_fused(c, st->g, fp, st->P[0], st->alpha_inv));        // global reduction #1, from the first factor
+  else BCG_TRY(phase_A(c, st->g, st->mass, sigma[0], st->T, st->P[0], st->alpha_inv));  // global reduction #1
   if (!st->alpha_inv.all_finite()) BCG_FAIL(c, BCG_ERR_NUMERIC, "SBCGrQ: P^dagger A P is not finite");
   st->alpha = bcg::inverse_full_pivot(st->alpha_inv);    // :142
   // :145 uses delta of the previous iteration.  Sum mode: every X_s update is Y += P_s (a_s M) -- the residue folded into
@@ -641,12 +676,16 @@ int sbcgrq_iteration(bcg_sbcgrq_state* st, bcg_sbcgrq_trace* trace, bool more_fo
   if (!st->pending.empty()) {  // the old block is needed by a later phase C: the new one goes to another buffer
     // ... a spare one, or, in the iteration that closes a full group, T itself: phase B reads each tile of T just before
     // it writes the same tile of the new Q, and T is not read again before the next operator application rewrites it
+    // (fused: T is not in use at all -- it is the free buffer)
     const bool over_T = st->Qfree.empty();
     bcg_field* out = over_T ? st->T : st->Qfree.back();
-    BCG_TRY(phase_B(c, st->Q, st->T, st->alpha, G2, st->q_lazy ? &st->q_rinv : nullptr, out));  // global reduction #2
+    if (fused) BCG_TRY(phase_B_fused(c, st->g, fp, st->Q, st->alpha, G2, st->q_lazy ? &st->q_rinv : nullptr, out));
+    else BCG_TRY(phase_B(c, st->Q, st->T, st->alpha, G2, st->q_lazy ? &st->q_rinv : nullptr, out));  // global reduction #2
     if (over_T) st->T = nullptr;  // one of the group's buffers takes its place below
     else st->Qfree.pop_back();
     st->Q = out;  // the old buffer stays with pending.back()
+  } else if (fused) {
+    BCG_TRY(phase_B_fused(c, st->g, fp, st->Q, st->alpha, G2, st->q_lazy ? &st->q_rinv : nullptr, nullptr));
   } else {
     BCG_TRY(phase_B(c, st->Q, st->T, st->alpha, G2, st->q_lazy ? &st->q_rinv : nullptr));  // global reduction #2
   }
@@ -1045,6 +1084,62 @@ int bcg_sbcgrq_solve_sum(bcg_context* c, const bcg_gauge* g, double mass, bcg_fi
   const int rc = bcg_sbcgrq_iterate(st, max_iterations, iterations_out, residual_out, trace);
   bcg_sbcgrq_end(st);
   return rc;
+}
+
+// Test aid, not part of the interface: the first factor with its Gram product as the solver launches it on the fused path,
+// W = (mu - D) P copied out of the operator's tmp; the matrix is read with bcg_debug_phase_a_gram / _gram_raw.
+// BCG_ERR_UNSUPPORTED where the solver would not take that path.
+int bcg_debug_fused_first_factor(bcg_context* c, const bcg_gauge* g, double mass, double sigma0, bcg_field* W, const bcg_field* P) {
+  DeviceScope on_device(c);
+  if (!c || !g || !same_shape(W, P) || W == P || g->ctx != c || P->ctx != c) return BCG_ERR_INVALID;
+  FusedPair fp;
+  if (!plan_fused_pair(c, P, mass, sigma0, fp)) BCG_FAIL(c, BCG_ERR_UNSUPPORTED, "bcg_debug_fused_first_factor: the fused pair is not taken on this context");
+  CMat G;
+  BCG_TRY(phase_A_fused(c, g, fp, P, G));
+  bcg_field* tmp;
+  BCG_TRY(get_tmp(c, P->m, &tmp));
+  HIP_TRY(c, hipMemcpyAsync(W->d, tmp->d, field_bytes(W), hipMemcpyDeviceToDevice, c->stream));
+  return stream_sync(c);
+}
+
+// Test aids, not part of the interface (no declaration in include/): phase B of one iteration from given operands, by the
+// launches the solver takes.  W = (mu - D) P_0 is the first factor's output; alpha and rinv (may be null) are m x m complex,
+// column-major; G2 receives Qout^dagger Qout as the host uses it.  fused != 0: the second factor with phase B inside (fails
+// with BCG_ERR_UNSUPPORTED where the solver would not take that path); 0: T = (mu + D) W by the pair's second factor, then the
+// phase B kernel.  T is scratch (written only with fused == 0).
+int bcg_debug_phase_b_from_w(bcg_context* c, const bcg_gauge* g, double mass, double sigma0, const bcg_field* W, bcg_field* T,
+                             const bcg_field* Q, bcg_field* Qout, const double* alpha, const double* rinv, int fused, double* G2) {
+  DeviceScope on_device(c);
+  if (!c || !g || !W || !T || !Q || !Qout || !alpha || !G2 || !same_shape(W, Q) || !same_shape(W, T) || !same_shape(W, Qout) ||
+      g->ctx != c || W->ctx != c || W->m != 16 || W->parity >= 0)
+    return BCG_ERR_INVALID;
+  const int m = W->m;
+  FusedPair fp;
+  BCG_TRY(ensure_scratch(c));
+  const bool saved = c->hop_fused_b;
+  c->hop_fused_b = true;  // (the plans are the same either way; `fused` decides what is launched)
+  const bool ok = fused_pair(c, m, mass, sigma0, fp);
+  c->hop_fused_b = saved;
+  if (!ok) BCG_FAIL(c, BCG_ERR_UNSUPPORTED, "bcg_debug_phase_b_from_w: the factored pair is not taken on this context");
+  bcg_field* tmp;
+  BCG_TRY(get_tmp(c, m, &tmp));
+  BCG_TRY(halo_gauge(c, const_cast<bcg_gauge*>(g)));
+  HIP_TRY(c, hipMemcpyAsync(tmp->d, W->d, field_bytes(W), hipMemcpyDeviceToDevice, c->stream));
+  const CMat a(m, alpha);
+  CMat r, G;
+  if (rinv) r = CMat(m, rinv);
+  if (fused) {
+    BCG_TRY(phase_B_fused(c, g, fp, const_cast<bcg_field*>(Q), a, G, rinv ? &r : nullptr, Qout));
+  } else {
+    const bcg::HopLaunchPlan f2 = plan_stencil(c, c->lat, c->hop_tune, {m, bcg::HOP_FACT2, true, 0, bcg::HopWindow(), true});
+    if (f2.form != bcg::HOP_FORM_BUNDLE) BCG_FAIL(c, BCG_ERR_UNSUPPORTED, "bcg_debug_phase_b_from_w: no bundle plan");
+    bcg::hop_launch(c->stream, f2, g->U, g->Ughost, tmp->d, c->halo_recv, T->d, nullptr, fp.mu, c->partials);
+    BCG_TRY(check_launch(c, "hop_shifted_gram"));
+    BCG_TRY(stream_sync(c));  // (its fold has left the tickets zero before phase B's fold takes them)
+    BCG_TRY(phase_B(c, const_cast<bcg_field*>(Q), T, a, G, rinv ? &r : nullptr, Qout));
+  }
+  G.store(G2);
+  return stream_sync(c);
 }
 
 }  // extern "C"

@@ -32,6 +32,10 @@ BCG_LAYOUT_FN int hop4b_bwd_links(int m, bool cb) { return (cb ? 4 : 3) * (64 / 
 BCG_LAYOUT_FN size_t hop4b_lds_bytes(int m, bool cb) {
   return size_t(16) * 4 * (2 * hop4b_row_slot(m) + (hop4b_share_images(m) ? 2 : 1) * (hop4b_fwd_links(m) + hop4b_bwd_links(m, cb)));
 }
+// k_hop4b_fusedB (m = 16): behind the sweep's 73 728 B, -alpha and rho_prev^-1 unpadded, 16 bytes per entry: 8 192 B, which
+// makes a block exactly half of a CU's 160 KB
+BCG_LAYOUT_FN size_t hop4b_fusedB_mats_bytes(int m) { return size_t(16) * 2 * m * m; }
+static_assert(2 * (hop4b_lds_bytes(16, false) + hop4b_fusedB_mats_bytes(16)) == 160 * 1024, "fused phase B: two blocks per CU");
 // every form: the block reduction of the fused Gram product re-uses the memory (4 waves x 8 x 64 doubles)
 constexpr size_t kHopGramLdsBytes = 8 * 4 * 8 * 64;
 }  // namespace bcg

@@ -107,8 +107,12 @@ HopLaunchPlan hop_plan(const LatticeDev& lat, int max_blocks, const HopTuning& t
   };
   if (w.list && pl.grid == 0) return accept(HOP_FORM_ROW, 0);  // no boundary tiles
   // the factored pair exists in the bundle sweep only: whole full-volume fields at m = 16, FACT2 with its Gram product
-  const bool fact = mode == HOP_FACT1 || mode == HOP_FACT2;
-  if (fact && (m != 16 || pl.win.cb || pl.win.ring > 0 || cls != 0 || gram != (mode == HOP_FACT2))) return none;
+  // (HOP_FACT1G, HOP_FACT2B -- the pair with phase B in the second factor: requests of their own, always with their Gram
+  // products, in the pipelined step only; the fused factor keeps 8 KB of LDS for its two matrices behind the sweep's)
+  const bool fused = mode == HOP_FACT1G || mode == HOP_FACT2B;
+  const bool fact = mode == HOP_FACT1 || mode == HOP_FACT2 || fused;
+  if (fused && BCG_HOP4B_PIPE == 0) return none;
+  if (fact && (m != 16 || pl.win.cb || pl.win.ring > 0 || cls != 0 || gram != (mode != HOP_FACT1))) return none;
   // the fused residual form: m = 16 with its Gram product, whole fields
   if (mode == HOP_RESID && (m != 16 || !gram || pl.win.ring > 0 || pl.win.cb)) return none;
   // the other Gram product is HOP_SHIFTED's: at m = 16 in every form, at m = 8 in the column and bundle forms
@@ -127,7 +131,7 @@ HopLaunchPlan hop_plan(const LatticeDev& lat, int max_blocks, const HopTuning& t
   // k_hop4b: the column sweep over 2 x 2 bundles (whole launches only: the tile classes stay with k_hop4c)
   if (bundle_ok(m, lat, tune, pl, w, cls, mode == HOP_PLAIN)) {
     pace_bundle(pl, m, tune);
-    return accept(HOP_FORM_BUNDLE, hop4b_lds_bytes(m, false));
+    return accept(HOP_FORM_BUNDLE, hop4b_lds_bytes(m, false) + (mode == HOP_FACT2B ? hop4b_fusedB_mats_bytes(m) : 0));
   }
   if (mode == HOP_RESID || fact) return none;  // the fused residual form and the factored pair exist in the bundle sweep only
   if (w.column) {

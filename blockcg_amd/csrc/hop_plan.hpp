@@ -16,7 +16,7 @@ enum HopForm {
 struct HopRequest {
   int m = 0;
   HopMode mode = HOP_PLAIN;
-  bool gram = false;         // the fused Gram product (HOP_SHIFTED: p^dagger out; HOP_RESID and HOP_FACT2 carry theirs)
+  bool gram = false;         // the fused Gram product (HOP_SHIFTED: p^dagger out; HOP_RESID, HOP_FACT2, HOP_FACT1G and HOP_FACT2B carry theirs)
   int tile_class = 0;        // 0 whole launch, 1 interior tiles, 2 boundary tiles (HopTuning::boundary_list)
   HopWindow win;
   bool fold_target = false;  // HopTuning::fold may be used: fold the Gram partials in the kernel where the form can
@@ -44,6 +44,7 @@ struct HopLaunchPlan {
 HopLaunchPlan hop_plan(const LatticeDev& lat, int max_blocks, const HopTuning& tune, const HopRequest& request);
 // Launches a plan whose form is not HOP_FORM_NONE; returns the grid (= the blocks that wrote Gram partials).
 int hop_launch(hipStream_t s, const HopLaunchPlan& plan, const double2* U, const double2* Ughost, const double2* in,
-               const double2* ghost, double2* out, const double2* p, double c0, double2* partials);
+               const double2* ghost, double2* out, const double2* p, double c0, double2* partials,
+               const double2* mats = nullptr, int has_rinv = 0);  // (HOP_FACT2B: [-alpha][rho_prev^-1], kernels.hpp)
 
 }  // namespace bcg

@@ -50,7 +50,7 @@ void launch_pack_faces(hipStream_t s, int m, const LatticeDev& lat, const double
 void launch_pack_gauge_faces(hipStream_t s, const LatticeDev& lat, const double2* U, double2* send);
 
 // ---- generic (any supported m) kernels ---------------------------------------------------------
-enum HopMode { HOP_PLAIN = 0, HOP_SHIFTED = 1, HOP_RESID = 2, HOP_FACT1 = 3, HOP_FACT2 = 4 };
+enum HopMode { HOP_PLAIN = 0, HOP_SHIFTED = 1, HOP_RESID = 2, HOP_FACT1 = 3, HOP_FACT2 = 4, HOP_FACT1G = 5, HOP_FACT2B = 6 };
 // HOP_PLAIN  : out = D in                          (K1, inc/dirac_op.hpp:14-21)
 // HOP_SHIFTED: out = c0 * p - D in                 (second D of op fused with K2 and K3)
 // HOP_RESID  : nothing is written; r = c0 * p - D in - b with b passed in `out`'s place, and the block partials of
@@ -61,6 +61,12 @@ enum HopMode { HOP_PLAIN = 0, HOP_SHIFTED = 1, HOP_RESID = 2, HOP_FACT1 = 3, HOP
 //              Gram product of FACT1's input with FACT2's output).  No `p`: the shift term is the stencil's own input,
 //              taken from the row the kernel already holds.  Whole-field launches of the bundle kernel at m = 16 only,
 //              hop_plan declines otherwise
+// HOP_FACT1G / HOP_FACT2B: the pair with phase B of the solver inside the second factor.
+//              FACT1G: FACT1 with the block partials of out^dagger out -- the first reduction, known before the second
+//              factor starts.  FACT2B: nothing of c0 * in + D in is written; with Q passed as `p` and the matrices
+//              [-alpha][rho_prev^-1] the launch writes out = (Q rho_prev^-1) - (c0 * in + D in) alpha, phase B's chain
+//              (k_phaseB), and leaves the block partials of out^dagger out.  Requests of their own (always with the Gram
+//              product), same conditions as the pair
 void launch_hop_generic(hipStream_t s, int m, const LatticeDev& lat, const double2* U, const double2* Ughost,
                         const double2* in, const double2* ghost, double2* out, HopMode mode, const double2* p,
                         double c0);

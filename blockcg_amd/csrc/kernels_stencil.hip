@@ -942,7 +942,8 @@ __device__ __forceinline__ void hop4b_body(const LatticeDev& lat, const double2*
                                            const double2* __restrict__ Ughost, const double2* __restrict__ in,
                                            const double2* __restrict__ ghost, double2* __restrict__ out,
                                            const double2* __restrict__ p, double c0, double2* __restrict__ partials,
-                                           const HopWalk& hw, const HopWindow& win) {
+                                           const HopWalk& hw, const HopWindow& win,
+                                           const double2* __restrict__ mats = nullptr, int has_rinv = 0) {
   static_assert(!GRAM || M == 16 || M == 8, "fused Gram accumulation: lane&15 = rhs index (m = 16) or (site parity, rhs) (m = 8)");
   constexpr bool RING_OUT = RING && MODE == HOP_PLAIN;
   constexpr bool RING_IN = RING && MODE == HOP_SHIFTED;
@@ -953,15 +954,20 @@ __device__ __forceinline__ void hop4b_body(const LatticeDev& lat, const double2*
   // separate questions from here on, so that the memory pipeline of these modes cannot drift from the plain form's:
   //   HAS_P  -- a global `p` is read (loads, addresses, the wait counts of the pipelined step);
   //   SHIFT  -- the epilogue has a c0 term (from `p`, or from the own row).
-  constexpr bool FACT = MODE == HOP_FACT1 || MODE == HOP_FACT2;
+  // FUSEB (HOP_FACT2B): the second factor with phase B of the solver in its tail -- see "FUSEB" in the pipelined step.
+  constexpr bool FUSEB = MODE == HOP_FACT2B;
+  constexpr bool FACT = MODE == HOP_FACT1 || MODE == HOP_FACT2 || FUSEB;
+  constexpr bool PLUS_D = MODE == HOP_FACT2 || FUSEB;  // c0 in + D in (the other shifted forms: c0 p - D in)
   constexpr bool HAS_P = MODE == HOP_SHIFTED || MODE == HOP_RESID;
   constexpr bool SHIFT = HAS_P || FACT;
   static_assert(!FACT || (M == 16 && !RING && !CB), "factored pair: whole full-volume fields at m = 16");
-  static_assert(!FACT || GRAM == (MODE == HOP_FACT2), "factored pair: the second factor carries the Gram product");
-  // The second factor's Gram product is W^dagger W, a block with itself: gram_self_step and gram_self_block_store
-  // (mfma_common.hpp), two matrix instructions per colour instead of four.  Only the matrix instructions of the tail and
-  // the final store differ; the vector-memory sequence and the wait counts are those of every other mode.
-  constexpr bool SELF_GRAM = MODE == HOP_FACT2 && kSelfGramProducts != 4;
+  static_assert(!PLUS_D || GRAM, "factored pair: the second factor carries a Gram product");
+  // A factor's Gram product is a block with itself -- the second factor's input W (HOP_FACT2), the first factor's output W
+  // (HOP_FACT1 with GRAM: the same matrix, one launch earlier), the new residual block (FUSEB): gram_self_step and
+  // gram_self_block_store (mfma_common.hpp), two matrix instructions per colour instead of four.  Only the matrix
+  // instructions of the tail and the final store differ; the vector-memory sequence and the wait counts are those of every
+  // other mode (FUSEB: with the Q rows in p's place).
+  constexpr bool SELF_GRAM = FACT && GRAM && kSelfGramProducts != 4;
   // CB (checkerboard, half-volume fields -- kernels_generic.hip "Half-volume fields"): `in` holds the sites of one parity,
   // `out` / `p` those of the other, both in the compact order, and `lat` is the COMPACT lattice (L[0] = half the row).  A
   // row (x1, x2, x3) of the output has r = (x1 + x2 + x3 + parity of out) & 1 and its compact site k is x0 = 2 k + r; the
@@ -1016,6 +1022,23 @@ __device__ __forceinline__ void hop4b_body(const LatticeDev& lat, const double2*
   const char* const ghb = reinterpret_cast<const char*>(ghost);
   GramAcc<16> G;
   if (GRAM) gram_zero(G);
+  // FUSEB: -alpha and rho_prev^-1 behind the stencil's own LDS, 4 KB each, element (j_in, j_out) at 16 j_in + j_out: as the
+  // B operand of the matrix instruction (k = lane >> 4, n = lane & 15) lane l reads entry 64 s + l in k-step s -- linear,
+  // no padding needed.  Visible to every wave behind the barrier that opens the first column.
+  using vd4 = d4;  // (the walk below has a coordinate of that name)
+  dv2* const Ma = reinterpret_cast<dv2*>(smem) + hop4b_lds_bytes(M, CB) / 16;
+  dv2* const Mr = Ma + M * M;
+  if constexpr (FUSEB) {
+    for (int e = tid; e < M * M; e += NW * 64) {
+      const int at = (e % M) * M + e / M;  // global: column-major, element (i, j) at j M + i
+      const double2 a = mats[e];
+      Ma[at] = dv2{a.x, a.y};
+      if (has_rinv) {
+        const double2 b = mats[M * M + e];
+        Mr[at] = dv2{b.x, b.y};
+      }
+    }
+  }
 
   // ---- this block's tile inside a patch, and the patches of its XCD class
   const int r0 = hw.p0 / SPW, r1 = hw.p1 / 2, r4 = L0 / hw.p0, r5 = L1 / hw.p1, r6 = L2 / hw.p2;
@@ -1468,7 +1491,19 @@ __device__ __forceinline__ void hop4b_body(const LatticeDev& lat, const double2*
         asm volatile("" : "+v"(q1[0]), "+v"(q1[1]), "+v"(q1[2]), "+v"(q2[0]), "+v"(q2[1]), "+v"(q2[2]));
       }
       constexpr int nB = 3 + 2 * NHD;                               // row DMAs
-      constexpr int nE = HAS_P ? 3 : 0;                             // p (the factored pair reads none: the plain form's counts)
+      // p (the factored pair reads none: the plain form's counts; FUSEB: the wave's Q rows in p's place, four per lane)
+      constexpr int nE = HAS_P ? 3 : (FUSEB ? 4 : 0);
+      // FUSEB: byte offsets of this lane's Q elements in the wave's 12 rows (3 KB, contiguous).  With rho_prev^-1 to apply the
+      // rows are an A operand (row i = lane & 15 = site + 4 colour, k = lane >> 4): elements 4 s + k of that row, s = 0 .. 3;
+      // lanes of the four rows a tile of 16 has beyond the wave's 12 repeat colour 2 (rows of a matrix product are independent:
+      // what they produce is never looked at).  Without, the lane's own three elements as the stencil holds them (and one again).
+      unsigned qo[4] = {0, 0, 0, 0};
+      if constexpr (FUSEB) {
+        const int i16 = lane & 15, ic = (i16 >> 2) < 3 ? (i16 >> 2) : 2;
+        const unsigned qa0 = static_cast<unsigned>((((i16 & 3) * 3 + ic) * M + (lane >> 4)) * 16);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) qo[s] = has_rinv ? qa0 + s * 64 : voff + (s < 3 ? s : 2) * M * 16;
+      }
       // link DMAs of this wave (checkerboard form: the forward links and all four directions' backward links, every wave)
       const int nC = CB ? RFW + 4 * RBK : RFW + 1 + (e1 ? 0 : RBK) + (e2 ? 0 : RBK);
       constexpr int nD = 6, nS = 3;
@@ -1688,6 +1723,15 @@ __device__ __forceinline__ void hop4b_body(const LatticeDev& lat, const double2*
           pv[2] = ld_sv_async<2 * M * 16>(prow, voff);
           asm volatile("; ASYNC_ISSUED p");
         }
+        dv2 qv[4];
+        if (FUSEB) {
+          asm volatile("; ASYNC_ISSUE q");
+          qv[0] = ld_sv_async<0>(prow, qo[0]);
+          qv[1] = ld_sv_async<0>(prow, qo[1]);
+          qv[2] = ld_sv_async<0>(prow, qo[2]);
+          qv[3] = ld_sv_async<0>(prow, qo[3]);
+          asm volatile("; ASYNC_ISSUED q");
+        }
         constexpr bool C_PIECES = SP_C && INCR && !CB;  // (closed-form / checkerboard link DMAs stay one group)
         const unsigned imgn = __builtin_amdgcn_readfirstlane(lds_addr_of(image(x3 + 1, wave)));
 #define BCG_LINK_PIECE(I)                                                                                    \
@@ -1809,15 +1853,95 @@ __device__ __forceinline__ void hop4b_body(const LatticeDev& lat, const double2*
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
           if (!SHIFT) tv[r] = make_double2(0.5 * acc[r].x, 0.5 * acc[r].y);
-          else if (MODE == HOP_FACT2) tv[r] = make_double2(fma(c0, pw[r].x, 0.5 * acc[r].x), fma(c0, pw[r].y, 0.5 * acc[r].y));
+          else if (PLUS_D) tv[r] = make_double2(fma(c0, pw[r].x, 0.5 * acc[r].x), fma(c0, pw[r].y, 0.5 * acc[r].y));
           else tv[r] = make_double2(fma(c0, pw[r].x, -0.5 * acc[r].x), fma(c0, pw[r].y, -0.5 * acc[r].y));
-          st_nt(reinterpret_cast<double2*>(orow + voff + r * M * 16), tv[r]);
+          if (!FUSEB) st_nt(reinterpret_cast<double2*>(orow + voff + r * M * 16), tv[r]);
+        }
+        // ---- FUSEB: phase B of the solver on the wave's 12 rows of T = tv, which is not written:
+        //   Q' = (Q rho_prev^-1) - T alpha,  the partials of Q'^dagger Q'.
+        // k_phaseB (kernels_mfma.hip) forms out^T = C^T in^T: the coefficients are the A operand of the matrix instruction, the
+        // rows its B operand.  Here the roles are exchanged -- rows the A operand, coefficients the B operand -- so that the
+        // accumulator fragment (row (lane >> 4) + 4 reg, column lane & 15) IS the stencil's ownership with reg = colour,
+        // row = site + 4 colour: the product lands where the stores and the Gram product want it, and only T has to change
+        // hands.  Every element is the same chain as in rmul_acc: the same products a * b (commutative) summed over k in the
+        // same order onto the same accumulator, K separately from zero and folded last.
+        // T changes ownership through LDS that is dead in the tail and this wave's alone: the two halo sites of its row slot
+        // of THIS slice (read at the top of the step by this wave only; the next DMA into them is issued behind the next
+        // barrier) take sites 0 and 1, its backward links of this slice (read at the top; rewritten by the link DMA of the next
+        // step) sites 2 and 3 -- the forward links and the own sites of the slot stay: the partner waves read them.
+        double2 qn[3];
+        if constexpr (FUSEB) {
+          dv2* const slot_h = Cbase + ((x3 & 1) * NW + wave) * CS;
+          dv2* const img_b = image(x3, wave) + NFW;
+          static_assert(!FUSEB || NBW >= 2 * 3 * M, "two sites of T fit the backward links of an image");
+          auto chunk = [&](int site) __attribute__((always_inline)) {
+            return (site & 2) ? img_b + (site & 1) * 3 * M : slot_h + (site & 1) * (SPW + 1) * 3 * M;
+          };
+          dv2* const tw = chunk(sw);
+#pragma unroll
+          for (int c = 0; c < 3; ++c) tw[c * M + j] = dv2{tv[c].x, tv[c].y};
+          wait_vmcnt(more ? nC + nD : 0);  // Q
+          dv2 qw[4];
+          asm volatile("; ASYNC_RETIRE q\n\tv_mov_b64 %0, %8\n\tv_mov_b64 %1, %9\n\tv_mov_b64 %2, %10\n\tv_mov_b64 %3, %11\n\t"
+                       "v_mov_b64 %4, %12\n\tv_mov_b64 %5, %13\n\tv_mov_b64 %6, %14\n\tv_mov_b64 %7, %15"
+                       : "=&v"(qw[0].x), "=&v"(qw[0].y), "=&v"(qw[1].x), "=&v"(qw[1].y), "=&v"(qw[2].x), "=&v"(qw[2].y),
+                         "=&v"(qw[3].x), "=&v"(qw[3].y)
+                       : "v"(qv[0].x), "v"(qv[0].y), "v"(qv[1].x), "v"(qv[1].y), "v"(qv[2].x), "v"(qv[2].y), "v"(qv[3].x),
+                         "v"(qv[3].y));
+          // one call of rmul_acc at M = 16 with the operands exchanged: (AR, AI) += x C, x the A operand, C in LDS at Ml
+          auto rmul_rows = [&](vd4& AR, vd4& AI, const dv2* x, const dv2* Ml) __attribute__((always_inline)) {
+            if constexpr (kGauss3M<16>) {
+              vd4 K = vd4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+              for (int s = 0; s < 4; ++s) {
+                const dv2 cd = Ml[64 * s + lane];
+                K = mfma(x[s].x + x[s].y, cd.x, K);
+                AR = mfma_nega(x[s].y, cd.x + cd.y, AR);
+                AI = mfma(x[s].x, cd.y - cd.x, AI);
+              }
+              rmul_gauss_fold(AR, AI, K);
+            } else {
+#pragma unroll
+              for (int s = 0; s < 4; ++s) {
+                const dv2 cd = Ml[64 * s + lane];
+                AR = mfma(x[s].x, cd.x, AR);
+                AR = mfma_nega(x[s].y, cd.y, AR);
+              }
+#pragma unroll
+              for (int s = 0; s < 4; ++s) {
+                const dv2 cd = Ml[64 * s + lane];
+                AI = mfma(x[s].x, cd.y, AI);
+                AI = mfma(x[s].y, cd.x, AI);
+              }
+            }
+          };
+          vd4 AR = vd4{0.0, 0.0, 0.0, 0.0}, AI = vd4{0.0, 0.0, 0.0, 0.0};
+          if (has_rinv) {
+            rmul_rows(AR, AI, qw, Mr);
+          } else {  // (fourth entry: the repeated load -- a row of the tile that is never looked at, but a defined value)
+            AR = vd4{qw[0].x, qw[1].x, qw[2].x, qw[3].x};
+            AI = vd4{qw[0].y, qw[1].y, qw[2].y, qw[3].y};
+          }
+          const int i16 = lane & 15, ic = (i16 >> 2) < 3 ? (i16 >> 2) : 2;
+          const dv2* const tr = chunk(i16 & 3) + ic * M + (lane >> 4);
+          dv2 ta[4];
+#pragma unroll
+          for (int s = 0; s < 4; ++s) ta[s] = tr[4 * s];
+          rmul_rows(AR, AI, ta, Ma);
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            qn[c] = make_double2(AR[c], AI[c]);
+            st_nt(reinterpret_cast<double2*>(orow + voff + c * M * 16), qn[c]);
+          }
         }
         if (GRAM) {
 #pragma unroll
           for (int r = 0; r < 3; ++r) {
-            if constexpr (SELF_GRAM) gram_self_step(G, &pw[r]);  // FACT2: W^dagger W as a self-product
-            else gram_step<16>(G, &pw[r], FACT ? &pw[r] : &tv[r]);
+            // the self-products: W = the second factor's input (HOP_FACT2) or the first factor's output, the new Q (FUSEB)
+            const double2* const self = FUSEB ? &qn[r] : (PLUS_D ? &pw[r] : &tv[r]);
+            if constexpr (SELF_GRAM) gram_self_step(G, self);
+            else if (FACT) gram_step<16>(G, self, self);
+            else gram_step<16>(G, &pw[r], &tv[r]);
           }
         }
         BCG_STAMPB(10)  // U_3 carried, wait for p, output, stores
@@ -1848,6 +1972,7 @@ __device__ __forceinline__ void hop4b_body(const LatticeDev& lat, const double2*
       }
     } else
     for (int x3 = win.x3_lo; x3 < x3_end; ++x3) {
+      static_assert(!(FUSEB || (MODE == HOP_FACT1 && GRAM)), "the first factor's Gram product and the fused phase B exist in the pipelined step only");
       const int step_n = vs0 + x3;
       if (hw.sync != nullptr && tid == 0 && pace) {  // pacing: all blocks of this XCD class within `sync_window` slices
         const int need = step_n - hw.sync_window;
@@ -2098,7 +2223,10 @@ __device__ __forceinline__ void hop4b_body(const LatticeDev& lat, const double2*
     if (M == 8) gram_block_store_fold8<NW>(G, smem, partials, tid, hw.fold.out != nullptr);  // two sites per 16-lane row: see the fold
     else if constexpr (SELF_GRAM) gram_self_block_store<NW>(G, smem, partials, tid, hw.fold.out != nullptr);
     else gram_block_store<16, NW>(G, smem, partials, tid, hw.fold.out != nullptr);
-    gram_fold<M * M>(hw.fold, partials, tid, NW * 64);
+    // (FUSEB: the fold's flag in a word of the dynamic LDS behind the reduction buffer -- a static word would be the block's
+    //  81 921st byte and the CU would hold one block)
+    if constexpr (FUSEB) gram_fold<M * M, true>(hw.fold, partials, tid, NW * 64, reinterpret_cast<int*>(smem + NW * 8 * 64));
+    else gram_fold<M * M>(hw.fold, partials, tid, NW * 64);
   }
 #undef BO_F
 #undef BO_SEL
@@ -2111,8 +2239,24 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
     double2* __restrict__ partials, HopWalk hw, HopWindow win) {
   hop4b_body<M, MODE, GRAM, RING, CB>(lat, U, Ughost, in, ghost, out, p, c0, partials, hw, win);
 }
+#if BCG_HOP4B_PIPE
+// The second factor fused with phase B (HOP_FACT2B): `p` = Q, `out` = the new Q (may be Q), mats = [-alpha][rho_prev^-1]
+// (m x m complex, column-major; the second only if has_rinv).  Dynamic LDS: the bundle sweep's and 8 KB for the matrices --
+// exactly half a CU's 160 KB.
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) k_hop4b_fusedB(
+    LatticeDev lat, const double2* __restrict__ U, const double2* __restrict__ Ughost, const double2* __restrict__ in,
+    const double2* __restrict__ ghost, double2* out, const double2* p, double c0, double2* __restrict__ partials, HopWalk hw,
+    HopWindow win, const double2* __restrict__ mats, int has_rinv) {
+  hop4b_body<16, HOP_FACT2B, true, false>(lat, U, Ughost, in, ghost, out, p, c0, partials, hw, win, mats, has_rinv);
+}
+#endif
 
 #ifdef BCG_PROBE  // tuning aid: compile only the probed stencil instantiations (seconds instead of minutes)
+#if BCG_HOP4B_PIPE
+template __global__ void k_hop4b<16, HOP_FACT1, true, false>(LatticeDev, const double2*, const double2*, const double2*,
+                                                              const double2*, double2*, const double2*, double, double2*,
+                                                              HopWalk, HopWindow);
+#endif
 template __global__ void k_hop4b<16, HOP_PLAIN, false, false>(LatticeDev, const double2*, const double2*, const double2*,
                                                                const double2*, double2*, const double2*, double, double2*,
                                                                HopWalk, HopWindow);
@@ -2140,7 +2284,8 @@ template __global__ void k_hop4c<16, HOP_SHIFTED, true, 0, false>(LatticeDev, co
 // exists for HOP_SHIFTED at m = 16 and, in the column and bundle forms, at m = 8; RESID and the factored pair at m = 16).
 template <int M>
 static void launch_hop4(hipStream_t s, const HopLaunchPlan& pl, const HopWalk& hw, const double2* U, const double2* Ughost,
-                        const double2* in, const double2* ghost, double2* out, const double2* p, double c0, double2* partials) {
+                        const double2* in, const double2* ghost, double2* out, const double2* p, double c0, double2* partials,
+                        const double2* mats, int has_rinv) {
   const HopWindow& win = pl.win;
   const bool gram = pl.req.gram, ring = win.ring > 0;
   const int mode = pl.req.mode, ntiles = pl.ntiles, cls = pl.tile_list ? 0 : pl.req.tile_class;  // (a list holds exactly the launch's tiles)
@@ -2163,6 +2308,10 @@ static void launch_hop4(hipStream_t s, const HopLaunchPlan& pl, const HopWalk& h
     if (mode == HOP_RESID) BCG_LAUNCH((k_hop4b<16, HOP_RESID, true, false>), hw, win);
     else if (mode == HOP_FACT1) BCG_LAUNCH((k_hop4b<16, HOP_FACT1, false, false>), hw, win);
     else if (mode == HOP_FACT2) BCG_LAUNCH((k_hop4b<16, HOP_FACT2, true, false>), hw, win);
+#if BCG_HOP4B_PIPE
+    else if (mode == HOP_FACT1G) BCG_LAUNCH((k_hop4b<16, HOP_FACT1, true, false>), hw, win);
+    else if (mode == HOP_FACT2B) BCG_LAUNCH(k_hop4b_fusedB, hw, win, mats, has_rinv);
+#endif
     else if (gram && M == 16) BCG_LAUNCH4B_R(16, HOP_SHIFTED, true);
     else if (gram) BCG_LAUNCH4B_R(8, HOP_SHIFTED, true);
     else if (mode == HOP_PLAIN) BCG_LAUNCH4B_R(M, HOP_PLAIN, false);
@@ -2200,15 +2349,17 @@ static void launch_hop4(hipStream_t s, const HopLaunchPlan& pl, const HopWalk& h
 }
 
 int hop_launch(hipStream_t s, const HopLaunchPlan& pl, const double2* U, const double2* Ughost, const double2* in,
-               const double2* ghost, double2* out, const double2* p, double c0, double2* partials) {
+               const double2* ghost, double2* out, const double2* p, double c0, double2* partials, const double2* mats,
+               int has_rinv) {
   assert(pl.form != HOP_FORM_NONE && "hop_launch: a declined plan (the caller runs a generic kernel instead)");
   if (pl.grid == 0) return 0;  // an empty tile list
   HopWalk hw{pl.p0, pl.p1, pl.p2, pl.xcd_split, pl.sync, pl.sync_window, pl.sync_stride, pl.sync_limit, pl.tile_list, pl.list_n,
              pl.fold, pl.super};
   if (hw.sync) (void)hipMemsetAsync(hw.sync, 0, sizeof(unsigned) * 8 * hw.sync_stride, s);
-  if (pl.req.m == 8) launch_hop4<8>(s, pl, hw, U, Ughost, in, ghost, out, p, c0, partials);
-  else if (pl.req.m == 16) launch_hop4<16>(s, pl, hw, U, Ughost, in, ghost, out, p, c0, partials);
-  else launch_hop4<32>(s, pl, hw, U, Ughost, in, ghost, out, p, c0, partials);
+  assert((pl.req.mode != HOP_FACT2B || mats != nullptr) && "hop_launch: the fused phase B needs its matrices");
+  if (pl.req.m == 8) launch_hop4<8>(s, pl, hw, U, Ughost, in, ghost, out, p, c0, partials, mats, has_rinv);
+  else if (pl.req.m == 16) launch_hop4<16>(s, pl, hw, U, Ughost, in, ghost, out, p, c0, partials, mats, has_rinv);
+  else launch_hop4<32>(s, pl, hw, U, Ughost, in, ghost, out, p, c0, partials, mats, has_rinv);
   return pl.grid;
 }
 

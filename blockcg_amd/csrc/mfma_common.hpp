@@ -492,10 +492,22 @@ __device__ __forceinline__ double2 sum_sc1(const double2* p, int64_t stride, int
   }
   return make_double2(sr, si);
 }
-template <int NV>
-__device__ __forceinline__ void gram_fold(const GramFold& gf, double2* __restrict__ partials, int tid, int nthreads) {
+// gram_fold's block-wide flag: a static LDS word, or (ROLE_IN_DYNAMIC: a kernel whose dynamic LDS is exactly half a CU's
+// and must stay two blocks per CU -- the stencil factor fused with phase B) a word of the caller's dynamic LDS
+template <bool ROLE_IN_DYNAMIC>
+__device__ __forceinline__ int& gram_fold_role(int* dynamic_word) {
+  if constexpr (ROLE_IN_DYNAMIC) {
+    return *dynamic_word;
+  } else {
+    __shared__ int s_role_static;
+    return s_role_static;
+  }
+}
+template <int NV, bool ROLE_IN_DYNAMIC = false>
+__device__ __forceinline__ void gram_fold(const GramFold& gf, double2* __restrict__ partials, int tid, int nthreads,
+                                          int* dynamic_word = nullptr) {
   if (gf.out == nullptr) return;
-  __shared__ int s_role;
+  int& s_role = gram_fold_role<ROLE_IN_DYNAMIC>(dynamic_word);
   const int nb = gridDim.x, g = blockIdx.x & 7;
   const int in_group = (nb - g + 7) >> 3;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's write-through partial stores have reached the L2

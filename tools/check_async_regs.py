@@ -16,6 +16,12 @@ through the `!more` side of the step's tail, one that leaves the loop behind the
 (at most one of each kind, groups n1 and n2 only) are reported and tolerated; any further lost path, a lost path of another
 group, or a jump table fails the build (tests/test_build_checks.py feeds a synthetic loop-without-retire listing).
 
+The instantiations are found by name (every `k_hop4b...` function of the listing), so new ones are covered as they are
+added: the first factor with its Gram product (`k_hop4b<16, HOP_FACT1, true>`: the groups n1 / n2 of the plain form) and the
+second factor fused with phase B (`k_hop4b_fusedB`), whose Q rows travel in the group `q` -- issued in p's place, retired in
+the tail.  A listing that holds `k_hop4b_fusedB` without a group `q` fails: the loads would have become visible to hipcc or
+lost their markers.
+
 usage: tools/check_async_regs.py <device asm from `hipcc -S --cuda-device-only`>   exit status 1 on a violation
 """
 import re
@@ -40,6 +46,9 @@ def main(path):
         lines = m.group(2).split('\n')
         label = {l.split(':')[0]: i for i, l in enumerate(lines) if re.match(r'^\.LBB\w+:', l)}
         starts = [(i, l.split('ASYNC_ISSUE ')[1].split()[0]) for i, l in enumerate(lines) if 'ASYNC_ISSUE ' in l]
+        if 'k_hop4b_fusedB' in m.group(1) and 'q' not in {t for _, t in starts}:
+            print(m.group(1)[28:62], 'the fused phase B has no hand-waited group q: FAIL')
+            ok = False
         for i, tag in starts:
             seen += 1
             j = i + 1

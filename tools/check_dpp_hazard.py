@@ -8,6 +8,10 @@ s_waitcnt orders them) -- unless the register allocator puts a copy (v_mov, v_ac
 This script reads the device assembly and fails if, within the two instructions in front of any v_fmac_f64_dpp, a VALU
 instruction writes a register of its src0, or within five a v_cmpx / v_writelane... writes EXEC.
 
+Every v_fmac_f64_dpp of the listing is checked, whichever kernel it belongs to: the first factor with its Gram product and the
+second factor fused with phase B (k_hop4b_fusedB) share the directions' arithmetic and are covered with the rest.  The
+fused kernel exists in the broadcast form only: a listing that defines it without one such instruction fails.
+
 usage: tools/check_dpp_hazard.py <device asm from `hipcc -S --cuda-device-only`>   exit status 1 on a violation
 """
 import re
@@ -49,7 +53,14 @@ def main(path):
         print('   line %d: %s   ->   line %d: %s' % b)
     if n_dpp == 0:
         print('no v_fmac_f64_dpp found (not a BCAST build?)')
-    return 1 if bad else 0
+    # the fused kernel without a single broadcast FMA would mean its directions were compiled another way
+    missing = []
+    for m in re.finditer(r'^(_ZN3bcg\S*k_hop4b_fusedB[^:\s]*):[^\n]*\n(.*?)s_endpgm', open(path).read(), re.S | re.M):
+        if n_dpp and 'v_fmac_f64_dpp' not in m.group(2):
+            missing.append(m.group(1))
+    for name in missing:
+        print('no v_fmac_f64_dpp in', name[:80])
+    return 1 if bad or missing else 0
 
 
 if __name__ == '__main__':

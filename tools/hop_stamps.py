@@ -3,7 +3,9 @@
 k_hop4c: library built with -DBCG_HOP4C_STAMPS and BCG_HOP_BUNDLE=0; k_hop4b (the default form): -DBCG_HOP4B_STAMPS and
 `python tools/hop_stamps.py 4b`  (tools/build_variant.sh stamps "-DBCG_HOP4B_STAMPS"; BCG_LIB=...); `pipe`: the same build, the
 segments of the software-pipelined step; `fact2`: the second pass of the factored pair (HOP_FACT2, with its Gram product) of the
-solver's phase A instead of the plain hop, which leaves its stamps behind the Gram partials."""
+solver's phase A instead of the plain hop, which leaves its stamps behind the Gram partials -- with BCG_HOP_FUSED_B=0; with the
+default (1) both factors carry a Gram product and stamp the same place, so what is read is the later launch: the second
+factor fused with phase B (k_hop4b_fusedB), whose segment "carry U3, WAIT p, output, stores" holds phase B's products."""
 import ctypes
 import os
 import sys
