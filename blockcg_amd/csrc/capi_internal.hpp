@@ -1,6 +1,7 @@
 // Internals shared by the three files that implement include/blockcg_hip.h (round 5: blockcg_capi.hip split by subsystem):
 //   capi_context.hip    context, scratch and profiling, host <-> device transfers, field primitives, memory planning
-//   capi_operator.hip   halo exchange, the stencil launches, dirac_op::op (whole tmp, capacity ring, half-volume), gauge API
+//   capi_operator.hip   halo exchange, the stencil launches, dirac_op::op (half-volume, capacity ring, whole tmp), the factored
+//                       pair's planner and launchers (apply_shifted's and the solver's), gauge API
 //   capi_solvers.hip    SBCGrQ (phases A / B / C, grouped and deferred updates), CG, SCG, BCG, BCGrQ, true residuals
 //   capi_force.hip      the fermion force of multi-shift solutions (bcg_force_accumulate), gauge-field download / zero
 //   capi_sources.hip    noise fields, point / wall sources, the slice-resolved inner product
@@ -196,20 +197,26 @@ int reserve_operator_scratch(bcg_context* c, const bcg_field* like);
 // phase_A (capi_solvers.hip) is its only consumer
 int apply_shifted(bcg_context* c, const bcg_gauge* g, double mass, double sigma0, bcg_field* T, const bcg_field* P,
                   int* gram_blocks = nullptr, bool* gram_folded = nullptr, bool* gram_self = nullptr);
-// The factored pair with phase B of SBCGrQ inside the second factor (BCG_HOP_FUSED_B): the plans of both launches, made
-// before the first runs.  fused_pair: false where the path is not taken (the callers then run apply_shifted and phase B).
+// The factored pair A + sigma0 = (mu + D)(mu - D) at m = 16, in its operator form (apply_shifted) or with phase B of SBCGrQ
+// inside the second factor (the solver, under BCG_HOP_FUSED_B): the plans of both launches, made before the first runs.
 struct FusedPair {
   bcg::HopLaunchPlan f1, f2;
-  double mu = 0.0;  // sqrt(mass^2 + sigma0)
+  double mu = 0.0;       // sqrt(mass^2 + sigma0)
+  bool phase_b = false;  // phase B inside the second factor; the first factor then sums the Gram matrix
+  bool taken = false;    // false: the callers run the reference's two hops (and the phase B kernel)
 };
-bool fused_pair(const bcg_context* c, int m, double mass, double sigma0, FusedPair& fp);
-int fused_first_factor(bcg_context* c, const bcg_gauge* g, const FusedPair& fp, const bcg_field* P, int* gram_blocks, bool* gram_folded);
-int fused_second_factor(bcg_context* c, const bcg_gauge* g, const FusedPair& fp, const bcg_field* Q, bcg_field* Qout,
-                        const double2* mats, bool has_rinv, int* gram_blocks, bool* gram_folded);
+// plan_pair decides (the one list of who may take the pair) and plans; the launchers own tmp, the booking and check_launch
+int plan_pair(bcg_context* c, const bcg_field* P, double mass, double sigma0, bool with_phase_b, bool fold, FusedPair& fp);
+int pair_first_factor(bcg_context* c, const bcg_gauge* g, const FusedPair& fp, const bcg_field* P, int* gram_blocks = nullptr,
+                      bool* gram_folded = nullptr);
+int pair_second_factor(bcg_context* c, const bcg_gauge* g, const FusedPair& fp, bcg_field* out, const bcg_field* Q,
+                       const double2* mats, bool has_rinv, int* gram_blocks, bool* gram_folded);
 
 // ---- capi_solvers.hip ------------------------------------------------------------------------------
 // Phase A of an iteration: T = (A + sigma0) P ; G = P^dagger T   (:134-140)
-int phase_A(bcg_context* c, const bcg_gauge* g, double mass, double sigma0, bcg_field* T, const bcg_field* P, CMat& G);
+// fused (a taken pair with phase B inside): the first factor alone, G = W^dagger W from its own output; T is not touched
+int phase_A(bcg_context* c, const bcg_gauge* g, double mass, double sigma0, bcg_field* T, const bcg_field* P, CMat& G,
+            const FusedPair* fused = nullptr);
 int pair_shifts_depth(const bcg_context* c, int m, int n_shifts);
 int thin_qr(bcg_context* c, bcg_field* y, CMat& R);  // thinQR (inc/fields.hpp:140-146)
 

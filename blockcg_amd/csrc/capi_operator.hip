@@ -228,6 +228,14 @@ bcg::HopLaunchPlan plan_stencil(const bcg_context* c, const bcg::LatticeDev& lat
   if (rq.fold_target) tune.fold = bcg::GramFold{c->dev_gram, c->fold_tickets};
   return bcg::hop_plan(lat, kFastBlocks, tune, rq);
 }
+// The same for both launches of the factored pair (hop_plan_pair): whole fields on the context's own lattice and tuning
+static bcg::HopPairPlan plan_stencil_pair(const bcg_context* c, int m, bool with_phase_b, bool fold) {
+  if (c->force_generic) return bcg::HopPairPlan();
+  assert(c->hop_tune.sync.counters && c->fold_tickets && "plan_stencil_pair: ensure_scratch comes first");
+  bcg::HopTuning tune = c->hop_tune;
+  if (fold) tune.fold = bcg::GramFold{c->dev_gram, c->fold_tickets};
+  return bcg::hop_plan_pair(c->lat, kFastBlocks, tune, m, with_phase_b, fold);
+}
 
 // Half-volume fields: the compact lattice (x0 halved) with the half ghost faces -- half the sites at half the offsets,
 // compact in x0 like the field
@@ -566,159 +574,74 @@ int reserve_operator_scratch(bcg_context* c, const bcg_field* like) {
   return BCG_OK;
 }
 
-// Phase A of a solver (T and G = P^dagger T wanted together) on whole full-volume fields at m = 16, both launches on the
-// bundle sweep of an undivided lattice: A + sigma0 = mu^2 - D^2 = (mu + D)(mu - D) with mu = sqrt(mass^2 + sigma0), D
-// anti-Hermitian for any links.  W = (mu - D) P, T = (mu + D) W, G = P^dagger T = W^dagger W: neither pass reads a field
-// other than its stencil input (the second pass of the other form reads P besides: a third of its traffic), and G is a
-// self-product.  Everything else -- bcg_dirac_apply, true residuals, capacity mode, half fields, other widths, divided
-// lattices, the row form of the sweep -- keeps the other form's kernels.  BCG_HOP_FACTORED=0 (read at context creation)
-// switches it off.  DESIGN.md section 4.
-// (f1, f2: the plans of the two factors, both made before the first runs; the pair is taken only if both are bundle plans)
-static bool factored_pair(const bcg_context* c, int m, double c0, bool want_gram, bool fold, bcg::HopLaunchPlan& f1,
-                          bcg::HopLaunchPlan& f2) {
-  if (!c->hop_factored || !want_gram || m != 16 || !(c0 > 0.0) || c->distributed || c->force_tile_classes || !fast_hop(c, m))
-    return false;  // (distributed: some direction is divided over ranks)
-  f1 = plan_stencil(c, c->lat, c->hop_tune, {m, bcg::HOP_FACT1, false});
-  f2 = plan_stencil(c, c->lat, c->hop_tune, {m, bcg::HOP_FACT2, true, 0, bcg::HopWindow(), fold});
-  return f1.form == bcg::HOP_FORM_BUNDLE && f2.form == bcg::HOP_FORM_BUNDLE;
+// ---- the factored pair ---------------------------------------------------------------------------------
+// Whole full-volume fields at m = 16, both launches on the bundle sweep of an undivided lattice: A + sigma0 = mu^2 - D^2 =
+// (mu + D)(mu - D) with mu = sqrt(mass^2 + sigma0), D anti-Hermitian for any links.  W = (mu - D) P, T = (mu + D) W,
+// G = P^dagger T = W^dagger W: neither pass reads a field other than its stencil input (the second pass of the other form
+// reads P besides: a third of its traffic), and G is a self-product.  Two uses:
+//   the operator form (apply_shifted with the Gram product asked for -- phase A of a solver): the second factor writes T;
+//   with phase B of SBCGrQ inside (BCG_HOP_FUSED_B, default on; asked for by the solver): G needs no T, so the first factor
+//     sums it from its own output, alpha = G^-1 is on the host before the second factor starts, and that launch applies phase
+//     B's update to each site's T while it is on chip.  T is neither written nor read -- 2 s of the 3 s phase B moved -- and
+//     the phase B launch is gone.
+// Everything else -- bcg_dirac_apply, true residuals, capacity mode, half fields, other widths, divided lattices, the row form
+// of the sweep -- keeps the other form's kernels.  BCG_HOP_FACTORED=0 (read at context creation) switches the pair off.
+// pair_admitted: every condition under which operands of width m and this parity may take the pair at c0 = mass^2 + sigma0
+static bool pair_admitted(const bcg_context* c, int m, int parity, double c0) {
+  return c->hop_factored && m == 16 && parity < 0 &&       // whole full-volume fields (half fields keep their kernels)
+         c0 > 0.0 &&                                       // a real mu
+         !c->distributed &&                                // no direction divided over ranks
+         !c->force_tile_classes && fast_hop(c, m) && !capacity_path(c, m);
 }
-
-// T = (mass^2 + sigma0) P - D(D(P))   [op + add(P, sigma0), inc/block_solvers.hpp:134-136]
-int apply_shifted(bcg_context* c, const bcg_gauge* g, double mass, double sigma0, bcg_field* T, const bcg_field* P,
-                  int* gram_blocks, bool* gram_folded, bool* gram_self) {
-  if (gram_folded) *gram_folded = false;
-  if (gram_self) *gram_self = false;
-  if (P->parity >= 0) {  // A restricted to one parity: tmp (other parity) = D P, T = (mass^2 + sigma0) P - D tmp
-    if (gram_blocks) *gram_blocks = 0;
-    if (T->parity != P->parity) BCG_FAIL(c, BCG_ERR_INVALID, "half-volume operator: result and argument must have the same parity");
-    const int m = P->m;
-    bcg_field* tmp;
-    BCG_TRY(get_tmp_half(c, m, 1 - P->parity, &tmp));
-    BCG_TRY(halo_gauge(c, const_cast<bcg_gauge*>(g)));
-    // the bundle sweep in its checkerboard form (m = 16, 32, compact row a multiple of the tile, patch walk, direction 0 not
-    // divided over ranks), else the generic kernel
-    // (algorithmic bytes of these launches: two link passes per half site -- all the lattice's links, see apply_shifted_ring)
-    const bool fast = fast_hop(c, m) && c->lat.L[0] > 1;
-    const bool gram = gram_blocks != nullptr && m == 16;  // the fused product exists at m = 16 (as in the full-volume sweep)
-    // direction 3 whole, split exchange available: the sweep in x3 chunks with every exchange overlapped -- provided the
-    // checkerboard bundle sweep takes EVERY window the chunked sweep launches.  The chunked sweep has no generic fallback
-    // once its first exchange is posted; a tuning that switches the bundle walk off (BCG_HOP_BUNDLE=0, an odd
-    // BCG_HOP_PATCH) or a slice too small for the grid lands in the blocking path below, which falls back to k_hop_half.
-    if (fast) BCG_TRY(ensure_scratch(c));
-    SweepPlans sweep;
-    if (fast && half_chunked_path(c) && plan_sweep(c, P, tmp, gram, sweep))
-      return apply_shifted_ring(c, g, mass, sigma0, T, P, gram_blocks, sweep, tmp);
-    BCG_TRY(halo_field(c, P));  // (a lattice divided over ranks: the half faces of the source, then below those of tmp)
-    bcg::HopLaunchPlan p1, p2;  // both checkerboard launches, planned before the first
-    if (fast) {
-      const bcg::LatticeDev latc = compact_lattice(c->lat);
-      p1 = plan_stencil(c, latc, c->hop_tune, {m, bcg::HOP_PLAIN, false, 0, {0, 0, 0, 1, tmp->parity}});
-      p2 = plan_stencil(c, latc, c->hop_tune, {m, bcg::HOP_SHIFTED, gram, 0, {0, 0, 0, 1, T->parity}, gram && gram_folded});
-    }
-    const bool cb = p1.form != bcg::HOP_FORM_NONE && p2.form != bcg::HOP_FORM_NONE, cb_gram = cb && gram;
-    if (cb) note_stencil_form(c, p1), note_stencil_form(c, p2);
-    {
-      ProfScope ps(c, "hop_half", alg_bytes(c, m, 2, 2, 1, 2), hop_flops(c, m, false, 1, 2));
-      if (cb) bcg::hop_launch(c->stream, p1, g->U, g->Ughost, P->d, c->halo_recv, tmp->d, nullptr, 0.0, c->partials);
-      else bcg::launch_hop_half(c->stream, m, c->lat, tmp->parity, g->U, g->Ughost, P->d, c->halo_recv, tmp->d, bcg::HOP_PLAIN, nullptr, 0.0);
-    }
-    BCG_TRY(check_launch(c, "hop_half"));
-    BCG_TRY(halo_field(c, tmp));
-    const double c0 = mass * mass + sigma0;
-    {
-      ProfScope ps(c, cb_gram ? "hop_half_shifted_gram" : "hop_half_shifted", alg_bytes(c, m, 3, 2, 1, 2), hop_flops(c, m, cb_gram, 1, 2));
-      if (cb) {
-        const int nb = bcg::hop_launch(c->stream, p2, g->U, g->Ughost, tmp->d, c->halo_recv, T->d, P->d, c0, c->partials);
-        if (gram) *gram_blocks = nb;
-        if (p2.fold.out) *gram_folded = true;
-      } else {
-        bcg::launch_hop_half(c->stream, m, c->lat, T->parity, g->U, g->Ughost, tmp->d, c->halo_recv, T->d, bcg::HOP_SHIFTED, P->d, c0);
-      }
-    }
-    return check_launch(c, "hop_half_shifted");
-  }
-  if (fast_hop(c, P->m)) BCG_TRY(ensure_scratch(c));
-  if (capacity_path(c, P->m)) {
-    SweepPlans sweep;  // (nothing is posted or launched before every window of the sweep has its plan)
-    if (!plan_sweep(c, P, nullptr, gram_blocks != nullptr, sweep)) BCG_FAIL(c, BCG_ERR_UNSUPPORTED, "capacity mode: stencil window rejected");
-    return apply_shifted_ring(c, g, mass, sigma0, T, P, gram_blocks, sweep);
-  }
-  bcg_field* tmp;
-  BCG_TRY(get_tmp(c, P->m, &tmp));
-  bcg::HopLaunchPlan f1, f2;
-  if (factored_pair(c, P->m, mass * mass + sigma0, gram_blocks != nullptr, gram_folded != nullptr, f1, f2)) {
-    // mu * mu differs from mass^2 + sigma0 by at most one ulp: a perturbation of sigma0 by 1e-16 (mass^2 + sigma0), about
-    // 1e-22 at mass 1e-3 -- far below the rounding of the operator itself (1e-16 |D^2 P|, |D^2| up to 16)
-    const double mu = std::sqrt(mass * mass + sigma0);
-    BCG_TRY(halo_gauge(c, const_cast<bcg_gauge*>(g)));
-    if (c->profiling) c->prof["stencil_form_factored_pair"].count += 1;
-    note_stencil_form(c, f1);
-    {  // W = (mu - D) P: the plain hop's streams
-      ProfScope ps(c, "hop", alg_bytes(c, P->m, 2, 1), hop_flops(c, P->m, false));
-      bcg::hop_launch(c->stream, f1, g->U, g->Ughost, P->d, c->halo_recv, tmp->d, nullptr, mu, c->partials);
-    }
-    BCG_TRY(check_launch(c, "hop"));
-    // T = (mu + D) W and the partials of W^dagger W = P^dagger T; tmp (= W) is read by this launch alone.
-    // The kernel forms the self-product in two real products and stores Im G = C - C^T (mfma_common.hpp:
-    // gram_self_step): what it sums is Hermitian with a real diagonal already, so for this path finish_gram's mirror of the
-    // lower triangle and phase_A's drop of Im G_ii (gram_self below) change no bit.  They stay for the other forms.
-    note_stencil_form(c, f2);
-    {
-      ProfScope ps(c, "hop_shifted_gram", alg_bytes(c, P->m, 2, 1), hop_flops(c, P->m, true));
-      *gram_blocks = bcg::hop_launch(c->stream, f2, g->U, g->Ughost, tmp->d, c->halo_recv, T->d, nullptr, mu, c->partials);
-    }
-    if (f2.fold.out) *gram_folded = true;
-    if (gram_self) *gram_self = true;
-    return check_launch(c, "hop_shifted_gram");
-  }
-  // as the reference writes it: tmp = D P, T = (mass^2 + sigma0) P - D tmp (with P^dagger T where asked)
-  BCG_TRY(hop(c, g, tmp, P, bcg::HOP_PLAIN, nullptr, 0.0));
-  return hop(c, g, T, tmp, bcg::HOP_SHIFTED, P, mass * mass + sigma0, gram_blocks, gram_folded);
-}
-
-// ---- the factored pair with phase B of SBCGrQ inside the second factor (BCG_HOP_FUSED_B, default on) ----
-// G = P^dagger T = W^dagger W needs no T: the first factor sums it from its own output (HOP_FACT1G), so alpha = G^-1 is on
-// the host before the second factor starts, and that launch (HOP_FACT2B) applies phase B's update to each site's T while it is
-// on chip: Q' = Q rho_prev^-1 - T alpha with the partials of Q'^dagger Q'.  T is neither written nor read -- 2 s of the 3 s
-// phase B moved -- and the phase B launch is gone.  Taken where factored_pair is, if both plans are bundle plans (both are made
-// before the first launch); everything else keeps apply_shifted and the phase B kernels.
-bool fused_pair(const bcg_context* c, int m, double mass, double sigma0, FusedPair& fp) {
+// fp.taken: operands like P take the pair, and both plans -- made here, before the first launch -- are bundle plans.
+// The form with phase B inside also needs the row kernels' width (the caller runs k_phaseB otherwise).
+int plan_pair(bcg_context* c, const bcg_field* P, double mass, double sigma0, bool with_phase_b, bool fold, FusedPair& fp) {
   const double c0 = mass * mass + sigma0;
-  if (!c->hop_fused_b || !c->hop_factored || m != 16 || !(c0 > 0.0) || c->distributed || c->force_tile_classes || !fast_hop(c, m) ||
-      !fast_rows(c, m) || capacity_path(c, m))
-    return false;
-  fp.f1 = plan_stencil(c, c->lat, c->hop_tune, {m, bcg::HOP_FACT1G, true, 0, bcg::HopWindow(), true});
-  fp.f2 = plan_stencil(c, c->lat, c->hop_tune, {m, bcg::HOP_FACT2B, true, 0, bcg::HopWindow(), true});
-  fp.mu = std::sqrt(c0);  // (as in apply_shifted)
-  return fp.f1.form == bcg::HOP_FORM_BUNDLE && fp.f2.form == bcg::HOP_FORM_BUNDLE;
+  fp = FusedPair();
+  if (!pair_admitted(c, P->m, P->parity, c0) || (with_phase_b && !fast_rows(c, P->m))) return BCG_OK;
+  BCG_TRY(ensure_scratch(c));
+  const bcg::HopPairPlan pp = plan_stencil_pair(c, P->m, with_phase_b, fold);
+  fp.f1 = pp.f1, fp.f2 = pp.f2, fp.taken = pp.taken, fp.phase_b = with_phase_b;
+  // mu * mu differs from mass^2 + sigma0 by at most one ulp: a perturbation of sigma0 by 1e-16 (mass^2 + sigma0), about
+  // 1e-22 at mass 1e-3 -- far below the rounding of the operator itself (1e-16 |D^2 P|, |D^2| up to 16)
+  fp.mu = std::sqrt(c0);
+  return BCG_OK;
 }
-// W = (mu - D) P into the operator's tmp, with the partials of W^dagger W
-int fused_first_factor(bcg_context* c, const bcg_gauge* g, const FusedPair& fp, const bcg_field* P, int* gram_blocks, bool* gram_folded) {
+// W = (mu - D) P into the operator's tmp: the plain hop's streams.  With phase B inside also the partials of W^dagger W
+// (gram_blocks, gram_folded; the operator form leaves them alone).
+int pair_first_factor(bcg_context* c, const bcg_gauge* g, const FusedPair& fp, const bcg_field* P, int* gram_blocks, bool* gram_folded) {
   bcg_field* tmp;
   BCG_TRY(get_tmp(c, P->m, &tmp));
   BCG_TRY(halo_gauge(c, const_cast<bcg_gauge*>(g)));
   if (c->profiling) c->prof["stencil_form_factored_pair"].count += 1;
   note_stencil_form(c, fp.f1);
+  int nb;
   {
-    ProfScope ps(c, "hop", alg_bytes(c, P->m, 2, 1), hop_flops(c, P->m, true));
-    *gram_blocks = bcg::hop_launch(c->stream, fp.f1, g->U, g->Ughost, P->d, c->halo_recv, tmp->d, nullptr, fp.mu, c->partials);
+    ProfScope ps(c, "hop", alg_bytes(c, P->m, 2, 1), hop_flops(c, P->m, fp.phase_b));
+    nb = bcg::hop_launch(c->stream, fp.f1, g->U, g->Ughost, P->d, c->halo_recv, tmp->d, nullptr, fp.mu, c->partials);
   }
-  *gram_folded = fp.f1.fold.out != nullptr;
+  if (fp.phase_b) *gram_blocks = nb, *gram_folded = fp.f1.fold.out != nullptr;
   return check_launch(c, "hop");
 }
-// Qout = Q [rho_prev^-1] - ((mu + D) W) alpha with the partials of Qout^dagger Qout; mats = [-alpha][rho_prev^-1] on the
-// device.  Qout may be Q: a wave has read its rows of Q when it writes them, and no other wave touches them.
+// From W in the operator's tmp, which this launch alone reads.  Operator form (Q, mats = nullptr): out = T = (mu + D) W and the
+// partials of W^dagger W = P^dagger T.  The kernel forms the self-product in two real products and stores Im G = C - C^T
+// (mfma_common.hpp: gram_self_step): what it sums is Hermitian with a real diagonal already, so for this path finish_gram's
+// mirror of the lower triangle and phase_A's drop of Im G_ii change no bit.  They stay for the other forms.
+// With phase B inside: out = Q [rho_prev^-1] - T alpha with the partials of out^dagger out; mats = [-alpha][rho_prev^-1] on
+// the device.  out may be Q: a wave has read its rows of Q when it writes them, and no other wave touches them.
 // Booking: existing tests pin the classes -- with the factored pair on, hop_shifted_gram has hop's count and hop's bytes, and
 // phaseB is counted once per iteration.  So the launch goes under hop_shifted_gram with its time, the stencil's streams
 // (2 s + g) and the stencil's and the Gram product's flops; phase B's share -- Q read and Q' written, 2 s, and its products --
 // under phaseB with count 1 and NO time (bench.py prices only classes that have time); stencil_form_fused_phaseB counts the
 // launches.
-int fused_second_factor(bcg_context* c, const bcg_gauge* g, const FusedPair& fp, const bcg_field* Q, bcg_field* Qout,
-                        const double2* mats, bool has_rinv, int* gram_blocks, bool* gram_folded) {
+int pair_second_factor(bcg_context* c, const bcg_gauge* g, const FusedPair& fp, bcg_field* out, const bcg_field* Q,
+                       const double2* mats, bool has_rinv, int* gram_blocks, bool* gram_folded) {
+  const int m = out->m;
   bcg_field* tmp;
-  BCG_TRY(get_tmp(c, Q->m, &tmp));
+  BCG_TRY(get_tmp(c, m, &tmp));
+  BCG_TRY(halo_gauge(c, const_cast<bcg_gauge*>(g)));
   note_stencil_form(c, fp.f2);
-  if (c->profiling) {
+  if (fp.phase_b && c->profiling) {
     c->prof["stencil_form_fused_phaseB"].count += 1;
     bcg::ProfEntry& b = c->prof["phaseB"];
     b.count += 1;
@@ -726,12 +649,92 @@ int fused_second_factor(bcg_context* c, const bcg_gauge* g, const FusedPair& fp,
     b.flops += product_flops(Q, has_rinv ? 2 : 1);
   }
   {
-    ProfScope ps(c, "hop_shifted_gram", alg_bytes(c, Q->m, 2, 1), hop_flops(c, Q->m, true));
-    *gram_blocks = bcg::hop_launch(c->stream, fp.f2, g->U, g->Ughost, tmp->d, c->halo_recv, Qout->d, Q->d, fp.mu, c->partials, mats,
-                                   has_rinv ? 1 : 0);
+    ProfScope ps(c, "hop_shifted_gram", alg_bytes(c, m, 2, 1), hop_flops(c, m, true));
+    *gram_blocks = bcg::hop_launch(c->stream, fp.f2, g->U, g->Ughost, tmp->d, c->halo_recv, out->d, Q ? Q->d : nullptr, fp.mu,
+                                   c->partials, mats, has_rinv ? 1 : 0);
   }
-  *gram_folded = fp.f2.fold.out != nullptr;
+  if (gram_folded) *gram_folded = fp.f2.fold.out != nullptr;
   return check_launch(c, "hop_shifted_gram");
+}
+
+// A restricted to one parity: tmp (other parity) = D P, T = (mass^2 + sigma0) P - D tmp
+static int apply_shifted_half(bcg_context* c, const bcg_gauge* g, double mass, double sigma0, bcg_field* T, const bcg_field* P,
+                              int* gram_blocks, bool* gram_folded) {
+  if (gram_blocks) *gram_blocks = 0;
+  if (T->parity != P->parity) BCG_FAIL(c, BCG_ERR_INVALID, "half-volume operator: result and argument must have the same parity");
+  const int m = P->m;
+  bcg_field* tmp;
+  BCG_TRY(get_tmp_half(c, m, 1 - P->parity, &tmp));
+  BCG_TRY(halo_gauge(c, const_cast<bcg_gauge*>(g)));
+  // the bundle sweep in its checkerboard form (m = 16, 32, compact row a multiple of the tile, patch walk, direction 0 not
+  // divided over ranks), else the generic kernel
+  // (algorithmic bytes of these launches: two link passes per half site -- all the lattice's links, see apply_shifted_ring)
+  const bool fast = fast_hop(c, m) && c->lat.L[0] > 1;
+  const bool gram = gram_blocks != nullptr && m == 16;  // the fused product exists at m = 16 (as in the full-volume sweep)
+  // direction 3 whole, split exchange available: the sweep in x3 chunks with every exchange overlapped -- provided the
+  // checkerboard bundle sweep takes EVERY window the chunked sweep launches.  The chunked sweep has no generic fallback
+  // once its first exchange is posted; a tuning that switches the bundle walk off (BCG_HOP_BUNDLE=0, an odd
+  // BCG_HOP_PATCH) or a slice too small for the grid lands in the blocking path below, which falls back to k_hop_half.
+  if (fast) BCG_TRY(ensure_scratch(c));
+  SweepPlans sweep;
+  if (fast && half_chunked_path(c) && plan_sweep(c, P, tmp, gram, sweep))
+    return apply_shifted_ring(c, g, mass, sigma0, T, P, gram_blocks, sweep, tmp);
+  BCG_TRY(halo_field(c, P));  // (a lattice divided over ranks: the half faces of the source, then below those of tmp)
+  bcg::HopLaunchPlan p1, p2;  // both checkerboard launches, planned before the first
+  if (fast) {
+    const bcg::LatticeDev latc = compact_lattice(c->lat);
+    p1 = plan_stencil(c, latc, c->hop_tune, {m, bcg::HOP_PLAIN, false, 0, {0, 0, 0, 1, tmp->parity}});
+    p2 = plan_stencil(c, latc, c->hop_tune, {m, bcg::HOP_SHIFTED, gram, 0, {0, 0, 0, 1, T->parity}, gram && gram_folded});
+  }
+  const bool cb = p1.form != bcg::HOP_FORM_NONE && p2.form != bcg::HOP_FORM_NONE, cb_gram = cb && gram;
+  if (cb) note_stencil_form(c, p1), note_stencil_form(c, p2);
+  {
+    ProfScope ps(c, "hop_half", alg_bytes(c, m, 2, 2, 1, 2), hop_flops(c, m, false, 1, 2));
+    if (cb) bcg::hop_launch(c->stream, p1, g->U, g->Ughost, P->d, c->halo_recv, tmp->d, nullptr, 0.0, c->partials);
+    else bcg::launch_hop_half(c->stream, m, c->lat, tmp->parity, g->U, g->Ughost, P->d, c->halo_recv, tmp->d, bcg::HOP_PLAIN, nullptr, 0.0);
+  }
+  BCG_TRY(check_launch(c, "hop_half"));
+  BCG_TRY(halo_field(c, tmp));
+  const double c0 = mass * mass + sigma0;
+  {
+    ProfScope ps(c, cb_gram ? "hop_half_shifted_gram" : "hop_half_shifted", alg_bytes(c, m, 3, 2, 1, 2), hop_flops(c, m, cb_gram, 1, 2));
+    if (cb) {
+      const int nb = bcg::hop_launch(c->stream, p2, g->U, g->Ughost, tmp->d, c->halo_recv, T->d, P->d, c0, c->partials);
+      if (gram) *gram_blocks = nb;
+      if (p2.fold.out) *gram_folded = true;
+    } else {
+      bcg::launch_hop_half(c->stream, m, c->lat, T->parity, g->U, g->Ughost, tmp->d, c->halo_recv, T->d, bcg::HOP_SHIFTED, P->d, c0);
+    }
+  }
+  return check_launch(c, "hop_half_shifted");
+}
+
+// T = (mass^2 + sigma0) P - D(D(P))   [op + add(P, sigma0), inc/block_solvers.hpp:134-136]
+// The dispatcher: half fields -> capacity ring -> factored pair -> the reference's two hops
+int apply_shifted(bcg_context* c, const bcg_gauge* g, double mass, double sigma0, bcg_field* T, const bcg_field* P,
+                  int* gram_blocks, bool* gram_folded, bool* gram_self) {
+  if (gram_folded) *gram_folded = false;
+  if (gram_self) *gram_self = false;
+  if (P->parity >= 0) return apply_shifted_half(c, g, mass, sigma0, T, P, gram_blocks, gram_folded);
+  if (fast_hop(c, P->m)) BCG_TRY(ensure_scratch(c));
+  if (capacity_path(c, P->m)) {
+    SweepPlans sweep;  // (nothing is posted or launched before every window of the sweep has its plan)
+    if (!plan_sweep(c, P, nullptr, gram_blocks != nullptr, sweep)) BCG_FAIL(c, BCG_ERR_UNSUPPORTED, "capacity mode: stencil window rejected");
+    return apply_shifted_ring(c, g, mass, sigma0, T, P, gram_blocks, sweep);
+  }
+  FusedPair fp;  // the operator form: only where the caller wants T and G = P^dagger T together (phase A of a solver)
+  if (gram_blocks) BCG_TRY(plan_pair(c, P, mass, sigma0, /*with_phase_b=*/false, gram_folded != nullptr, fp));
+  if (fp.taken) {
+    BCG_TRY(pair_first_factor(c, g, fp, P));
+    BCG_TRY(pair_second_factor(c, g, fp, T, nullptr, nullptr, false, gram_blocks, gram_folded));
+    if (gram_self) *gram_self = true;
+    return BCG_OK;
+  }
+  // as the reference writes it: tmp = D P, T = (mass^2 + sigma0) P - D tmp (with P^dagger T where asked)
+  bcg_field* tmp;
+  BCG_TRY(get_tmp(c, P->m, &tmp));
+  BCG_TRY(hop(c, g, tmp, P, bcg::HOP_PLAIN, nullptr, 0.0));
+  return hop(c, g, T, tmp, bcg::HOP_SHIFTED, P, mass * mass + sigma0, gram_blocks, gram_folded);
 }
 
 }  // namespace bcg_impl

@@ -6,10 +6,12 @@
 namespace bcg_impl {
 
 // Phase A of an iteration: T = (A + sigma0) P ; G = P^dagger T   (:134-140)
-int phase_A(bcg_context* c, const bcg_gauge* g, double mass, double sigma0, bcg_field* T, const bcg_field* P, CMat& G) {
+int phase_A(bcg_context* c, const bcg_gauge* g, double mass, double sigma0, bcg_field* T, const bcg_field* P, CMat& G,
+            const FusedPair* fused) {
   int nb = 0;
-  bool folded = false, self = false;
-  BCG_TRY(apply_shifted(c, g, mass, sigma0, T, P, &nb, &folded, &self));
+  bool folded = false, self = fused != nullptr;
+  if (fused) BCG_TRY(pair_first_factor(c, g, *fused, P, &nb, &folded));
+  else BCG_TRY(apply_shifted(c, g, mass, sigma0, T, P, &nb, &folded, &self));
   if (nb > 0) {
     BCG_TRY(finish_gram(c, P->m, nb, G, true, folded));
     c->phaseA_gram_raw = CMat(P->m, c->pin_gram);  // (finish_gram has synchronised; test aid)
@@ -43,8 +45,11 @@ bool lazy_q_width(const bcg_context* c, int m) {
 
 // rinv_prev: the stored Q is the previous iteration's un-normalised block, to be multiplied by this first (nullptr: Q as it is)
 // Qout (fused kernel only): the new Q is written there and Q keeps the old block (pair_shifts below)
-int phase_B(bcg_context* c, bcg_field* Q, const bcg_field* T, const CMat& alpha, CMat& G2, const CMat* rinv_prev = nullptr,
-            bcg_field* Qout = nullptr) {
+// fused (the pair phase A ran with): the update is made inside the pair's second factor from W in the operator's tmp.  T is
+// not touched; the caller's field stays allocated and keeps its place in the rotation of residual buffers.  Such an iteration:
+// first factor, reduction #1, the inversion, the uploads of -alpha and rho_prev^-1, the fused launch, reduction #2.
+int phase_B(bcg_context* c, const bcg_gauge* g, const FusedPair* fused, bcg_field* Q, const bcg_field* T, const CMat& alpha, CMat& G2,
+            const CMat* rinv_prev = nullptr, bcg_field* Qout = nullptr) {
   const int m = Q->m;
   if (!fast_rows(c, m)) {
     if (Qout) BCG_FAIL(c, BCG_ERR_INVALID, "phase B: a separate output needs the fused kernel");
@@ -55,46 +60,19 @@ int phase_B(bcg_context* c, bcg_field* Q, const bcg_field* T, const CMat& alpha,
   const CMat* two[2] = {&na, rinv_prev};
   const double2* Md;
   BCG_TRY(upload_mats(c, m, two, rinv_prev ? 2 : 1, &Md));
-  int nb;
-  {
-    ProfScope ps(c, "phaseB", row_bytes(Q, 3), product_flops(Q, rinv_prev ? 3 : 2));  // [rho^-1,] alpha, Gram
-    nb = bcg::launch_phaseB(c->stream, m, rows_of(Q), Q->d, T->d, Md, c->partials, c->row_blocks_B, c->row_batched,
-                            bcg::GramFold{c->dev_gram, c->fold_tickets},
-                            rinv_prev ? Md + static_cast<size_t>(m) * m : nullptr, Qout ? Qout->d : nullptr);
+  int nb = 0;
+  bool folded = true;
+  if (fused) {
+    BCG_TRY(pair_second_factor(c, g, *fused, Qout ? Qout : Q, Q, Md, rinv_prev != nullptr, &nb, &folded));
+  } else {
+    {
+      ProfScope ps(c, "phaseB", row_bytes(Q, 3), product_flops(Q, rinv_prev ? 3 : 2));  // [rho^-1,] alpha, Gram
+      nb = bcg::launch_phaseB(c->stream, m, rows_of(Q), Q->d, T->d, Md, c->partials, c->row_blocks_B, c->row_batched,
+                              bcg::GramFold{c->dev_gram, c->fold_tickets},
+                              rinv_prev ? Md + static_cast<size_t>(m) * m : nullptr, Qout ? Qout->d : nullptr);
+    }
+    BCG_TRY(check_launch(c, "phaseB"));
   }
-  BCG_TRY(check_launch(c, "phaseB"));
-  return finish_gram(c, m, nb, G2, true, /*folded=*/true);
-}
-
-// Phases A and B on the factored pair with phase B inside the second factor (capi_operator.hip: fused_pair).  The order of an
-// iteration becomes: first factor, reduction #1, the inversion, the uploads of -alpha and rho_prev^-1, the fused launch,
-// reduction #2.  T is not written; the caller's T field stays allocated and keeps its place in the rotation of residual buffers.
-bool plan_fused_pair(bcg_context* c, const bcg_field* P, double mass, double sigma0, FusedPair& fp) {
-  const int m = P->m;
-  if (!c->hop_fused_b || m != 16 || P->parity >= 0 || !fast_hop(c, m)) return false;  // (half fields keep their kernels)
-  if (ensure_scratch(c) != BCG_OK) return false;
-  return fused_pair(c, m, mass, sigma0, fp);
-}
-int phase_A_fused(bcg_context* c, const bcg_gauge* g, const FusedPair& fp, const bcg_field* P, CMat& G) {
-  int nb = 0;
-  bool folded = false;
-  BCG_TRY(fused_first_factor(c, g, fp, P, &nb, &folded));
-  BCG_TRY(finish_gram(c, P->m, nb, G, true, folded));
-  c->phaseA_gram_raw = CMat(P->m, c->pin_gram);
-  for (int i = 0; i < P->m; ++i) G(i, i) = G(i, i).real();  // (exactly real already: gram_self_block_store; as in phase_A)
-  c->phaseA_gram = G;
-  return BCG_OK;
-}
-int phase_B_fused(bcg_context* c, const bcg_gauge* g, const FusedPair& fp, bcg_field* Q, const CMat& alpha, CMat& G2,
-                  const CMat* rinv_prev, bcg_field* Qout) {
-  const int m = Q->m;
-  const CMat na = -alpha;
-  const CMat* two[2] = {&na, rinv_prev};
-  const double2* Md;
-  BCG_TRY(upload_mats(c, m, two, rinv_prev ? 2 : 1, &Md));
-  int nb = 0;
-  bool folded = false;
-  BCG_TRY(fused_second_factor(c, g, fp, Q, Qout ? Qout : Q, Md, rinv_prev != nullptr, &nb, &folded));
   return finish_gram(c, m, nb, G2, true, folded);
 }
 
@@ -662,10 +640,10 @@ int sbcgrq_iteration(bcg_sbcgrq_state* st, bcg_sbcgrq_trace* trace, bool more_fo
   // T = (A + sigma_0) P_0 ; alpha_inv = P_0^dagger T                          :134-140
   ++st->iter;                                            // :137
   st->alpha_inv_old = st->alpha_inv;                     // :139
-  FusedPair fp;  // (both launches planned here, before the first)
-  const bool fused = plan_fused_pair(c, st->P[0], st->mass, sigma[0], fp);
-  if (fused) BCG_TRY(phase_A_fused(c, st->g, fp, st->P[0], st->alpha_inv));        // global reduction #1, from the first factor
-  else BCG_TRY(phase_A(c, st->g, st->mass, sigma[0], st->T, st->P[0], st->alpha_inv));  // global reduction #1
+  FusedPair fp;  // the pair with phase B inside its second factor: both launches planned here, before the first
+  if (c->hop_fused_b) BCG_TRY(plan_pair(c, st->P[0], st->mass, sigma[0], /*with_phase_b=*/true, /*fold=*/true, fp));
+  const FusedPair* const fused = fp.taken ? &fp : nullptr;
+  BCG_TRY(phase_A(c, st->g, st->mass, sigma[0], st->T, st->P[0], st->alpha_inv, fused));  // global reduction #1 (fused: from the first factor)
   if (!st->alpha_inv.all_finite()) BCG_FAIL(c, BCG_ERR_NUMERIC, "SBCGrQ: P^dagger A P is not finite");
   st->alpha = bcg::inverse_full_pivot(st->alpha_inv);    // :142
   // :145 uses delta of the previous iteration.  Sum mode: every X_s update is Y += P_s (a_s M) -- the residue folded into
@@ -673,21 +651,17 @@ int sbcgrq_iteration(bcg_sbcgrq_state* st, bcg_sbcgrq_trace* trace, bool more_fo
   const CMat alpha_delta = st->Y ? st->residue[0] * (st->alpha * st->delta) : st->alpha * st->delta;
   // Q -= T alpha ; Gram matrix of the new Q                                  :148, :152
   CMat G2;
-  if (!st->pending.empty()) {  // the old block is needed by a later phase C: the new one goes to another buffer
-    // ... a spare one, or, in the iteration that closes a full group, T itself: phase B reads each tile of T just before
-    // it writes the same tile of the new Q, and T is not read again before the next operator application rewrites it
-    // (fused: T is not in use at all -- it is the free buffer)
-    const bool over_T = st->Qfree.empty();
-    bcg_field* out = over_T ? st->T : st->Qfree.back();
-    if (fused) BCG_TRY(phase_B_fused(c, st->g, fp, st->Q, st->alpha, G2, st->q_lazy ? &st->q_rinv : nullptr, out));
-    else BCG_TRY(phase_B(c, st->Q, st->T, st->alpha, G2, st->q_lazy ? &st->q_rinv : nullptr, out));  // global reduction #2
+  // Nothing pending: in place.  Otherwise the old block is needed by a later phase C and the new one goes to another buffer:
+  // a spare one, or, in the iteration that closes a full group, T itself: phase B reads each tile of T just before
+  // it writes the same tile of the new Q, and T is not read again before the next operator application rewrites it
+  // (fused: T is not in use at all -- it is the free buffer)
+  const bool over_T = !st->pending.empty() && st->Qfree.empty();
+  bcg_field* const out = st->pending.empty() ? nullptr : (over_T ? st->T : st->Qfree.back());
+  BCG_TRY(phase_B(c, st->g, fused, st->Q, st->T, st->alpha, G2, st->q_lazy ? &st->q_rinv : nullptr, out));  // global reduction #2
+  if (out) {
     if (over_T) st->T = nullptr;  // one of the group's buffers takes its place below
     else st->Qfree.pop_back();
     st->Q = out;  // the old buffer stays with pending.back()
-  } else if (fused) {
-    BCG_TRY(phase_B_fused(c, st->g, fp, st->Q, st->alpha, G2, st->q_lazy ? &st->q_rinv : nullptr, nullptr));
-  } else {
-    BCG_TRY(phase_B(c, st->Q, st->T, st->alpha, G2, st->q_lazy ? &st->q_rinv : nullptr));  // global reduction #2
   }
   st->rho_old = st->rho;                                 // :150
   if (c->debug_fail_iter > 0 && st->iter == c->debug_fail_iter) G2(0, 0) = cd(std::nan(""), 0.0);  // test aid: BCG_DEBUG_FAIL_ITER
@@ -1093,9 +1067,10 @@ int bcg_debug_fused_first_factor(bcg_context* c, const bcg_gauge* g, double mass
   DeviceScope on_device(c);
   if (!c || !g || !same_shape(W, P) || W == P || g->ctx != c || P->ctx != c) return BCG_ERR_INVALID;
   FusedPair fp;
-  if (!plan_fused_pair(c, P, mass, sigma0, fp)) BCG_FAIL(c, BCG_ERR_UNSUPPORTED, "bcg_debug_fused_first_factor: the fused pair is not taken on this context");
+  if (c->hop_fused_b) BCG_TRY(plan_pair(c, P, mass, sigma0, /*with_phase_b=*/true, /*fold=*/true, fp));
+  if (!fp.taken) BCG_FAIL(c, BCG_ERR_UNSUPPORTED, "bcg_debug_fused_first_factor: the fused pair is not taken on this context");
   CMat G;
-  BCG_TRY(phase_A_fused(c, g, fp, P, G));
+  BCG_TRY(phase_A(c, g, mass, sigma0, /*T=*/nullptr, P, G, &fp));
   bcg_field* tmp;
   BCG_TRY(get_tmp(c, P->m, &tmp));
   HIP_TRY(c, hipMemcpyAsync(W->d, tmp->d, field_bytes(W), hipMemcpyDeviceToDevice, c->stream));
@@ -1114,30 +1089,21 @@ int bcg_debug_phase_b_from_w(bcg_context* c, const bcg_gauge* g, double mass, do
       g->ctx != c || W->ctx != c || W->m != 16 || W->parity >= 0)
     return BCG_ERR_INVALID;
   const int m = W->m;
-  FusedPair fp;
-  BCG_TRY(ensure_scratch(c));
-  const bool saved = c->hop_fused_b;
-  c->hop_fused_b = true;  // (the plans are the same either way; `fused` decides what is launched)
-  const bool ok = fused_pair(c, m, mass, sigma0, fp);
-  c->hop_fused_b = saved;
-  if (!ok) BCG_FAIL(c, BCG_ERR_UNSUPPORTED, "bcg_debug_phase_b_from_w: the factored pair is not taken on this context");
+  FusedPair fp;  // (`fused` decides which form of the pair is planned, whatever BCG_HOP_FUSED_B says)
+  BCG_TRY(plan_pair(c, W, mass, sigma0, fused != 0, /*fold=*/true, fp));
+  if (!fp.taken) BCG_FAIL(c, BCG_ERR_UNSUPPORTED, "bcg_debug_phase_b_from_w: the factored pair is not taken on this context");
   bcg_field* tmp;
   BCG_TRY(get_tmp(c, m, &tmp));
-  BCG_TRY(halo_gauge(c, const_cast<bcg_gauge*>(g)));
   HIP_TRY(c, hipMemcpyAsync(tmp->d, W->d, field_bytes(W), hipMemcpyDeviceToDevice, c->stream));
   const CMat a(m, alpha);
   CMat r, G;
   if (rinv) r = CMat(m, rinv);
-  if (fused) {
-    BCG_TRY(phase_B_fused(c, g, fp, const_cast<bcg_field*>(Q), a, G, rinv ? &r : nullptr, Qout));
-  } else {
-    const bcg::HopLaunchPlan f2 = plan_stencil(c, c->lat, c->hop_tune, {m, bcg::HOP_FACT2, true, 0, bcg::HopWindow(), true});
-    if (f2.form != bcg::HOP_FORM_BUNDLE) BCG_FAIL(c, BCG_ERR_UNSUPPORTED, "bcg_debug_phase_b_from_w: no bundle plan");
-    bcg::hop_launch(c->stream, f2, g->U, g->Ughost, tmp->d, c->halo_recv, T->d, nullptr, fp.mu, c->partials);
-    BCG_TRY(check_launch(c, "hop_shifted_gram"));
+  if (!fused) {
+    int nb;
+    BCG_TRY(pair_second_factor(c, g, fp, T, nullptr, nullptr, false, &nb, nullptr));
     BCG_TRY(stream_sync(c));  // (its fold has left the tickets zero before phase B's fold takes them)
-    BCG_TRY(phase_B(c, const_cast<bcg_field*>(Q), T, a, G, rinv ? &r : nullptr, Qout));
   }
+  BCG_TRY(phase_B(c, g, fused ? &fp : nullptr, const_cast<bcg_field*>(Q), T, a, G, rinv ? &r : nullptr, Qout));
   G.store(G2);
   return stream_sync(c);
 }

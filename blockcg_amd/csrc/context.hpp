@@ -59,8 +59,8 @@ struct bcg_context {
   bcg::HopTuning hop_tune;  // specialised stencil: tile walk, patch shape, grid, streaming hints
   bcg::CMat phaseA_gram;     // the last G = P^dagger (A + sigma0) P of a solver's phase A, as the host used it (bcg_debug_phase_a_gram)
   bcg::CMat phaseA_gram_raw; // the same as the device summed it, where a stencil kernel did: no mirror, no diagonal fix (bcg_debug_phase_a_gram_raw)
-  bool hop_factored = true;  // phase A at m = 16: A + sigma0 as the factored stencil pair (apply_shifted; BCG_HOP_FACTORED=0: off)
-  bool hop_fused_b = true;   // SBCGrQ at m = 16: phase B inside the pair's second factor (fused_pair; BCG_HOP_FUSED_B=0: off)
+  bool hop_factored = true;  // m = 16: A + sigma0 as the factored stencil pair, either use (plan_pair's condition; BCG_HOP_FACTORED=0: off)
+  bool hop_fused_b = true;   // SBCGrQ at m = 16: phase B inside the pair's second factor (asked by plan_pair's callers; BCG_HOP_FUSED_B=0: off)
 
   // scratch
   std::map<int, bcg_field*> tmp_field;   // per width: the `tmp` of dirac_op::op (inc/dirac_op.hpp:39); key m + 1000 (1 + parity)

@@ -143,4 +143,14 @@ HopLaunchPlan hop_plan(const LatticeDev& lat, int max_blocks, const HopTuning& t
   return accept(HOP_FORM_ROW, hop4_lds_bytes(m, gram ? 3 : 2));
 }
 
+// the one place that spells the pair's four requests
+HopPairPlan hop_plan_pair(const LatticeDev& lat, int max_blocks, const HopTuning& tune, int m, bool with_phase_b, bool fold) {
+  HopPairPlan pp;
+  const HopRequest first = {m, HOP_FACT1, false}, first_g = {m, HOP_FACT1G, true, 0, HopWindow(), fold};
+  pp.f1 = hop_plan(lat, max_blocks, tune, with_phase_b ? first_g : first);
+  pp.f2 = hop_plan(lat, max_blocks, tune, {m, with_phase_b ? HOP_FACT2B : HOP_FACT2, true, 0, HopWindow(), fold});
+  pp.taken = pp.f1.form == HOP_FORM_BUNDLE && pp.f2.form == HOP_FORM_BUNDLE;
+  return pp;
+}
+
 }  // namespace bcg

@@ -42,6 +42,15 @@ struct HopLaunchPlan {
 // Pure (no HIP call, no device memory touched).  Never honours part of a request: a Gram product the chosen form does not
 // have, a mode or a window it cannot serve give HOP_FORM_NONE.
 HopLaunchPlan hop_plan(const LatticeDev& lat, int max_blocks, const HopTuning& tune, const HopRequest& request);
+
+// Both launches of the factored pair (A + sigma0 = (mu + D)(mu - D), whole full-volume fields at m = 16), planned together:
+// HOP_FACT1 then HOP_FACT2, or with phase B of SBCGrQ inside the second factor HOP_FACT1G then HOP_FACT2B (kernels.hpp).
+// fold: HopRequest::fold_target of the launches that carry a Gram product.  Pure, like hop_plan.
+struct HopPairPlan {
+  HopLaunchPlan f1, f2;
+  bool taken = false;  // the pair exists in the bundle sweep only: both plans are HOP_FORM_BUNDLE
+};
+HopPairPlan hop_plan_pair(const LatticeDev& lat, int max_blocks, const HopTuning& tune, int m, bool with_phase_b, bool fold);
 // Launches a plan whose form is not HOP_FORM_NONE; returns the grid (= the blocks that wrote Gram partials).
 int hop_launch(hipStream_t s, const HopLaunchPlan& plan, const double2* U, const double2* Ughost, const double2* in,
                const double2* ghost, double2* out, const double2* p, double c0, double2* partials,

@@ -1,4 +1,4 @@
-"""Phase A at m = 16 as the factored stencil pair (capi_operator.hip: factored_pair):
+"""Phase A at m = 16 as the factored stencil pair (capi_operator.hip: plan_pair, pair_first_factor, pair_second_factor):
 A + sigma_0 = mu^2 - D^2 = (mu + D)(mu - D), W = (mu - D) P_0, T = (mu + D) W, G = W^dagger W, so that the second stencil pass
 reads no P_0.  BCG_HOP_FACTORED=0 keeps the other form (tmp = D P_0, T = (m^2 + sigma_0) P_0 - D tmp, G = P_0^dagger T).
 

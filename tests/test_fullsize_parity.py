@@ -2,7 +2,7 @@
 overrides, so 64^4 runs the bundle sweep k_hop4b with 512 blocks over 16x8x8 patches -- k_hop4c for the tile classes --
 the geometry bench.py times).
 
-Which entry point reaches which stencil kernels at 64^4, m = 16 (capi_operator.hip: apply_shifted, factored_pair):
+Which entry point reaches which stencil kernels at 64^4, m = 16 (capi_operator.hip: apply_shifted, plan_pair):
   D.D (bcg_dirac_hop)            k_hop4b<HOP_PLAIN>
   D.op (bcg_dirac_apply)         k_hop4b<HOP_PLAIN>, then k_hop4b<HOP_SHIFTED> without a Gram product
   phase A of SBCGrQ              the factored pair, k_hop4b<HOP_FACT1> and k_hop4b<HOP_FACT2> with its Gram product: the

@@ -1,6 +1,6 @@
-"""SBCGrQ at m = 16 with phase B inside the second stencil factor (capi_operator.hip: fused_pair; kernels_stencil.hip:
-k_hop4b<16, HOP_FACT1, GRAM> and k_hop4b_fusedB).  BCG_HOP_FUSED_B=0 keeps the factored pair and the
-phase B kernel.
+"""SBCGrQ at m = 16 with phase B inside the second stencil factor (capi_operator.hip: plan_pair with phase B inside and
+its two launchers, pair_first_factor and pair_second_factor; kernels_stencil.hip: k_hop4b<16, HOP_FACT1, GRAM> and
+k_hop4b_fusedB).  BCG_HOP_FUSED_B=0 keeps the pair's operator form and the phase B kernel.
 
 The first factor W = (mu - D) P_0 sums G = W^dagger W = P_0^dagger (A + sigma_0) P_0 from its own output, so alpha = G^-1 is on
 the host before the second factor starts; that launch forms T = (mu + D) W per site, applies Q' = Q rho_prev^-1 - T alpha on
@@ -18,7 +18,8 @@ take the same products in the same order with the operands' roles exchanged (row
 matrices (first reduction against hermitian_dot(P_0, dirac_apply P_0); second against k_phaseB's): 1e-13, the project's bound
 for one primitive (TOL_KERNEL).  Solves on against off: FORM_BOUND = 9e-14 of test_factored_stencil.py; against the oracle:
 that file's bounds (TOL_COEFF for the traces, 1e-10 for X_s).  Off against the parent commit's build: the SHA-256 of every X_s
-recorded from that build (tests/golden/fused_phase_b_parent.json)."""
+recorded from that build (tests/golden/fused_phase_b_parent.json).  On, and the two test aids, against the build before the
+pair's two renditions in host code became one: SHA-256 again (tests/golden/factored_pair_parent.json)."""
 import contextlib
 import ctypes
 import functools
@@ -38,6 +39,7 @@ M = 16
 SHAPES = {"16x8x8x8": [16, 8, 8, 8], "32x8x8x6": [32, 8, 8, 6], "32x4x4x3": [32, 4, 4, 3]}
 SEED_U, SEED_B = 171, 172  # (test_factored_stencil.py's: its oracle solves are shared)
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "fused_phase_b_parent.json")
+GOLDEN_PAIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "factored_pair_parent.json")
 
 
 @contextlib.contextmanager
@@ -258,6 +260,73 @@ def test_off_is_the_parent_build_bit_for_bit(shape, depth):
     """The X_s of BCG_HOP_FUSED_B=0 against the digests recorded from the parent commit's library (mass 1e-3, same inputs)."""
     want = json.load(open(GOLDEN))[f"{shape} depth {depth}"]
     assert _digest(_solve(shape, 1e-3, False, depth)[0]) == want
+
+
+# ---- the switch on: the pair's host code against the build before it became one pair ---------------------------------------
+# tests/golden/factored_pair_parent.json: SHA-256 digests recorded from the library of the commit before the two renditions
+# of the pair were merged into one (capi_operator.hip: plan_pair, pair_first_factor, pair_second_factor), same inputs.  The
+# Gram reductions sum in a fixed order (test_two_identical_solves_are_bit_identical), so equality is the bound.
+def _sha(a):
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+def _solve_on_digests(shape, depth):
+    X, trace, _ = _solve(shape, 1e-3, True, depth)
+    return {"X": _digest(X), **{key: _sha(trace[key]) for key in KEYS}}
+
+
+def _operator_form_digests(mass):
+    """One bcg_debug_phase_a on 16 x 8 x 8 x 8 -- the operator form of the pair, T = (mu + D)(mu - D) P and the partials of
+    W^dagger W: T and the Gram matrix as the device summed it."""
+    import blockcg_amd as bc
+    dims, U, _ = _inputs("16x8x8x8")
+    ctx = _context(dims)
+    ctx.profiling(True)
+    D = bc.dirac_op(ctx, mass, U=U)
+    P = bc.block_fermion_field(ctx, M, _random_field(ctx.V, 7))
+    T = bc.block_fermion_field(ctx, M)
+    fn = ctx.lib.bcg_debug_phase_a
+    fn.restype = ctypes.c_int
+    fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]
+    ctx.check(fn(ctx.h, D.h, mass, 0.0, T.h, P.h))
+    prof = ctx.profile()
+    assert _count(prof, "stencil_form_factored_pair") == 1 and "stencil_form_fused_phaseB" not in prof, sorted(prof)
+    return {"T": _sha(T.download()), "G_raw": _sha(_mat(ctx, "bcg_debug_phase_a_gram_raw"))}
+
+
+def _phase_b_aid_digests(fused, normalise):
+    """bcg_debug_phase_b_from_w on 16 x 8 x 8 x 8 at mass 1e-3 from operands that no launch of the library made: Q' and G2."""
+    import blockcg_amd as bc
+    dims, U, _ = _inputs("16x8x8x8")
+    ctx = _context(dims)
+    D = bc.dirac_op(ctx, 1e-3, U=U)
+    W = bc.block_fermion_field(ctx, M, _random_field(ctx.V, 11))
+    Q = bc.block_fermion_field(ctx, M, _random_field(ctx.V, 12))
+    T, out = bc.block_fermion_field(ctx, M), bc.block_fermion_field(ctx, M)
+    rng = np.random.default_rng(13)
+    alpha = 0.1 * (rng.normal(size=(M, M)) + 1j * rng.normal(size=(M, M))) + np.eye(M)
+    rinv = np.triu(rng.normal(size=(M, M)) + 1j * rng.normal(size=(M, M))) * 0.1 + np.diag(1.0 + 0.1 * rng.random(M))
+    G2 = _phase_b(ctx, D, 0.0, W, T, Q, out, alpha, rinv if normalise else None, fused=fused)
+    return {"Q": _sha(out.download()), "G2": _sha(G2)}
+
+
+@pytest.mark.parametrize("depth", [4, 1], ids=["groups-of-4", "no-groups"])
+@pytest.mark.parametrize("shape", sorted(SHAPES))
+def test_on_is_the_parent_build_bit_for_bit(shape, depth):
+    """Every X_s and every trace array of BCG_HOP_FUSED_B=1 against the digests recorded from the parent commit's library."""
+    assert _solve_on_digests(shape, depth) == json.load(open(GOLDEN_PAIR))[f"solve {shape} depth {depth}"]
+
+
+@pytest.mark.parametrize("mass", [0.2, 1e-3])
+def test_operator_form_is_the_parent_build_bit_for_bit(mass):
+    assert _operator_form_digests(mass) == json.load(open(GOLDEN_PAIR))[f"phase_a 16x8x8x8 mass {mass}"]
+
+
+@pytest.mark.parametrize("normalise", [True, False], ids=["rinv", "no-rinv"])
+@pytest.mark.parametrize("fused", [0, 1], ids=["fact2-phaseB", "fused"])
+def test_phase_b_aid_is_the_parent_build_bit_for_bit(fused, normalise):
+    want = json.load(open(GOLDEN_PAIR))[f"phase_b 16x8x8x8 fused {fused} {'rinv' if normalise else 'no-rinv'}"]
+    assert _phase_b_aid_digests(fused, normalise) == want
 
 
 # ---- where the path must not be taken ------------------------------------------------------------------------------------

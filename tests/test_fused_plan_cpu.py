@@ -1,7 +1,9 @@
 """The stencil planner (blockcg_amd/csrc/hop_plan.cpp) for the two requests of the factored pair with phase B inside the
 second factor: HOP_FACT1G (the first factor with its Gram product) and HOP_FACT2B (the fused launch).  Both are bundle plans
 exactly where the factored pair's are; the fused launch asks for the sweep's LDS and 8 192 B for its two matrices, which makes
-two blocks a CU's 160 KB.  Host code only (tests/cpp/fused_plan_probe.cpp): no GPU."""
+two blocks a CU's 160 KB.  And the pair planner (hop_plan_pair), which spells the requests of both uses of the pair for the
+library: its plans are hop_plan's for those requests, and the pair is taken exactly when both are bundle plans.
+Host code only (tests/cpp/fused_plan_probe.cpp): no GPU."""
 import os
 import shutil
 import subprocess
@@ -18,7 +20,7 @@ SMALL = dict(patch=(16, 2, 2), blocks=32)
 
 
 @pytest.fixture(scope="module")
-def plan(tmp_path_factory):
+def probe(tmp_path_factory):
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.fail("hipcc not found: the probe is compiled with the compiler that builds the library")
@@ -30,10 +32,16 @@ def plan(tmp_path_factory):
                    check=True)
     subprocess.run([hipcc, main, os.path.join(ROOT, "blockcg_amd", "_build", "hop_plan.o"), "-o", exe], check=True)
 
+    def run(what, *values):
+        line = " ".join(str(int(v)) for v in values)
+        return [int(v) for v in subprocess.run([exe, *what], input=line + "\n", check=True, capture_output=True, text=True).stdout.split()]
+    return run
+
+
+@pytest.fixture(scope="module")
+def plan(probe):
     def ask(dims, mode, gram=1, m=16, tune=SMALL, bundle=1, cls=0, x3n=0, ring=0, cb=0):
-        line = " ".join(str(v) for v in [m, *dims, *tune["patch"], tune["blocks"], bundle, cls, x3n, ring, cb, mode, gram])
-        form, lds, grid = subprocess.run([exe], input=line + "\n", check=True, capture_output=True, text=True).stdout.split()
-        return int(form), int(lds), int(grid)
+        return tuple(probe([], m, *dims, *tune["patch"], tune["blocks"], bundle, cls, x3n, ring, cb, mode, gram))
     return ask
 
 
@@ -59,3 +67,37 @@ def test_declined_elsewhere(plan, mode):
     assert plan(dims, mode, cls=1)[0] == 0                       # whole launches only
     assert plan(dims, mode, bundle=0)[0] == 0                    # the bundle sweep only: never a column or row plan
     assert plan([16, 8, 8, 8], mode, tune=DEFAULT)[0] == 0       # a lattice the default walk does not tile
+
+
+# ---- the pair planner ------------------------------------------------------------------------------------------------------
+# the four lattices of test_both_requests_are_bundle_plans, then the declined cases that mean something for a pair
+PAIR_CASES = {"64^4": dict(dims=[64, 64, 64, 64], tune=DEFAULT), "16x8x8x8": dict(dims=[16, 8, 8, 8]), "32x8x8x6": dict(dims=[32, 8, 8, 6]),
+              "32x4x4x3": dict(dims=[32, 4, 4, 3]), "m8": dict(dims=[16, 8, 8, 8], m=8, taken=False),
+              "m32": dict(dims=[16, 8, 8, 8], m=32, taken=False), "bundle0": dict(dims=[16, 8, 8, 8], bundle=0, taken=False),
+              "default-walk": dict(dims=[16, 8, 8, 8], tune=DEFAULT, taken=False)}
+FIELDS = 14  # form, LDS, grid, tiles, p0, p1, p2, xcd_split, super, paced, window, stride, limit, folds (print_plan)
+
+
+@pytest.mark.parametrize("fold", [0, 1])
+@pytest.mark.parametrize("with_phase_b", [0, 1], ids=["operator-form", "phase-B-inside"])
+@pytest.mark.parametrize("case", sorted(PAIR_CASES))
+def test_pair_plans_are_hop_plans_for_the_requests_as_spelled(probe, case, with_phase_b, fold):
+    kw = dict(PAIR_CASES[case])
+    dims, m, tune, bundle, taken = kw["dims"], kw.get("m", 16), kw.get("tune", SMALL), kw.get("bundle", 1), kw.get("taken", True)
+    head = [m, *dims, *tune["patch"], tune["blocks"], bundle]
+    got = probe(["pair"], *head, with_phase_b, fold)
+    assert len(got) == 1 + 2 * FIELDS
+    f1, f2 = got[1:1 + FIELDS], got[1 + FIELDS:]
+    # whole launches over all slices, no ring, full fields; the first factor of the operator form has no Gram product and
+    # is no fold target, every other launch carries its product and folds where the caller asked
+    if with_phase_b:
+        want1 = probe(["full"], *head, 0, 0, 0, 0, FACT1G, 1, fold)
+        want2 = probe(["full"], *head, 0, 0, 0, 0, FACT2B, 1, fold)
+    else:
+        want1 = probe(["full"], *head, 0, 0, 0, 0, FACT1, 0, 0)
+        want2 = probe(["full"], *head, 0, 0, 0, 0, FACT2, 1, fold)
+    assert f1 == want1 and f2 == want2
+    assert got[0] == int(f1[0] == BUNDLE and f2[0] == BUNDLE) == int(taken)
+    if taken:  # the fields are live: a folded launch where asked, and the long sweep of 64^4 is the paced one
+        assert f2[13] == fold and f1[13] == (fold if with_phase_b else 0)
+        assert f1[9] == f2[9] == int(case == "64^4")

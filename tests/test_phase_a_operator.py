@@ -1,4 +1,4 @@
-"""The factored stencil pair as an OPERATOR (capi_operator.hip: factored_pair; kernels_stencil.hip: k_hop4b<16, HOP_FACT1>,
+"""The factored stencil pair as an OPERATOR (capi_operator.hip: plan_pair; kernels_stencil.hip: k_hop4b<16, HOP_FACT1>,
 k_hop4b<16, HOP_FACT2>): one phase A of a solver, T = (A + sigma_0) P and G = P^dagger T, run once by the test aid
 bcg_debug_phase_a and held field by field against tests/phase_a_ref.py -- the unfactored T = (m^2 + sigma_0) P - D (D P) in
 extended precision with its own neighbour table, no mu anywhere -- over launch geometries, tuning, parameters of the
@@ -261,7 +261,7 @@ def test_parameters_of_the_factorisation(mass, sigma0):
 
 @pytest.mark.parametrize("mass,sigma0", [(0.0, 0.0), (0.2, -0.04 - 1e-3)])
 def test_pair_declines_without_a_positive_c0(mass, sigma0):
-    """c0 <= 0 has no real mu: factored_pair() declines, and the other form's kernels give the same T and G."""
+    """c0 <= 0 has no real mu: plan_pair() declines, and the other form's kernels give the same T and G."""
     name = "16x8x8x8"
     assert not mass * mass + sigma0 > 0.0
     run = _Run(name)
