@@ -11,4 +11,4 @@ from .api import (BlockCGError, Context, block_fermion_field, dirac_op, SBCGrQ, 
                   shift_sum, covariant_shift, laplacian, smear,
                   basis_dot, basis_slice_dot, basis_axpy, basis_slice_axpy, deflate, low_mode_solution, SBCGrQ_deflated,
                   basis_rotate, spectral_bound, lowest_modes, BASIS_ROTATE_MAX_COLUMNS,
-                  basis_slice_rotate, laplacian_modes)  # noqa: F401
+                  basis_slice_rotate, laplacian_modes, basis_slice_triple)  # noqa: F401

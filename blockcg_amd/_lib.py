@@ -135,6 +135,9 @@ SIGNATURES = {
                                            c_int_p, c_dbl_p]),
     "bcg_basis_slice_axpy": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                             c_int_p, c_dbl_p, c_int_p, ctypes.c_double]),
+    "bcg_basis_slice_triple": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,
+                                              ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int, ctypes.c_int, c_int_p, ctypes.c_int,
+                                              c_int_p, c_dbl_p]),
     "bcg_basis_rotate": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, c_dbl_p]),
     "bcg_spectral_bound": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_uint64, c_dbl_p]),

@@ -595,6 +595,41 @@ def basis_slice_axpy(y, V, C, dir, slices=None, momentum=None, beta=1.0):
     return y
 
 
+def basis_slice_triple(A, B, C, dir, slices=None, momenta=None):
+    """The baryon elementals of three lists of fields, slice by slice (include/blockcg_hip.h, bcg_basis_slice_triple):
+    [S, Ka, Kb, Kc] with entry (s, i, j, k) = sum over the sites x of slice x_dir = slices[s] of det[A_i(x), B_j(x), C_k(x)], the
+    colour determinant of three columns.  A, B, C as V in basis_dot, at most 64 columns each; they may share fields or be the
+    same list, and the same list three times gives a result that is antisymmetric bit for bit.  slices: a list of distinct
+    global slice indices (None: all L_dir slices in ascending order).  momenta as in basis_slice_dot: [P, S, Ka, Kb, Kc].
+    Summed over ranks and identical on every rank."""
+    A = list(A)
+    (Ah, na, Ka), (Bh, nb, Kb), (Ch, nc, Kc) = _basis_handles(A), _basis_handles(B), _basis_handles(C)
+    ctx = A[0].ctx
+    if not 0 <= int(dir) < ctx.ndim:
+        raise BlockCGError(1, "basis_slice_triple: direction outside the lattice")
+    if slices is None:
+        S, sl, n_slices = ctx.dims[int(dir)], None, 0
+    else:
+        arr = np.ascontiguousarray(list(slices), dtype=np.intc)
+        if arr.ndim != 1 or arr.size == 0:
+            raise BlockCGError(1, "basis_slice_triple: slices is a non-empty list of slice indices")
+        S, sl, n_slices = int(arr.size), arr.ctypes.data_as(_lib.c_int_p), int(arr.size)
+    if momenta is None:
+        out = np.empty((S, Kc, Kb, Ka), dtype=np.complex128)
+        ctx.check(ctx.lib.bcg_basis_slice_triple(Ah, na, Bh, nb, Ch, nc, int(dir), n_slices, sl, 0, None, _dp(out)))
+        return np.ascontiguousarray(out.transpose(0, 3, 2, 1))
+    mom = [list(p) for p in momenta]
+    if not mom or any(len(p) > 4 for p in mom):
+        raise BlockCGError(1, "basis_slice_triple: momenta is a non-empty list of up to 4 integers each")
+    ns = np.zeros((len(mom), 4), dtype=np.intc)
+    for k, p in enumerate(mom):
+        ns[k, :len(p)] = p
+    out = np.empty((len(mom), S, Kc, Kb, Ka), dtype=np.complex128)
+    ctx.check(ctx.lib.bcg_basis_slice_triple(Ah, na, Bh, nb, Ch, nc, int(dir), n_slices, sl, len(mom), ns.ctypes.data_as(_lib.c_int_p),
+                                             _dp(out)))
+    return np.ascontiguousarray(out.transpose(0, 1, 4, 3, 2))
+
+
 def deflate(B, V):
     """B <- B - V (V^dagger B) for an orthonormal basis V; returns C = V^dagger B, (K, m)."""
     C = basis_dot(V, B)

@@ -5,10 +5,13 @@
 // resolved by slice and momentum (bcg_basis_slice_dot; kernels: kernels_basis_slice.hip, plan: slice_plan.hpp), whose
 // P x L_dir x K x m result is assembled in the same buffer, and its adjoint, the update by slice (bcg_basis_slice_axpy;
 // kernels: kernels_basis_slice_axpy.hip, plan: slice_plan.hpp), whose matrices, phase table and slice lists are uploaded there.
+// And the baryon elementals of three lists (bcg_basis_slice_triple; kernels: kernels_basis_slice_triple.hip, plan:
+// slice_plan.hpp), whose P x S x K_c x K_b x K_a result is assembled in c->dev_basis from block partials in c->dev_triple.
 #include "capi_slice.hpp"
 #include "kernels_basis.hpp"
 #include "kernels_basis_slice.hpp"
 #include "kernels_basis_slice_axpy.hpp"
+#include "kernels_basis_slice_triple.hpp"
 
 namespace bcg_impl {
 namespace {
@@ -376,6 +379,133 @@ int bcg_basis_slice_axpy(bcg_field* y, const bcg_field* const* V, int nv, int di
     first = false;
   }
   return BCG_OK;
+}
+
+int bcg_basis_slice_triple(const bcg_field* const* A, int na, const bcg_field* const* B, int nb, const bcg_field* const* C, int nc, int dir,
+                           int n_slices, const int* slices, int n_mom, const int* momenta, double* out) {
+  const char* const who = "bcg_basis_slice_triple";
+  const bcg_field* like = A && na >= 1 ? A[0] : nullptr;
+  DeviceScope on_device(like ? like->ctx : nullptr);
+  const bcg_field* const* lists[3] = {A, B, C};
+  const int counts[3] = {na, nb, nc};
+  int64_t K[3];
+  for (int l = 0; l < 3; ++l) K[l] = basis_columns(lists[l], counts[l], like);
+  if (K[0] < 0 || K[1] < 0 || K[2] < 0 || !out) return BCG_ERR_INVALID;
+  bcg_context* c = like->ctx;
+  BCG_TRY(check_slice_dir(c, who, dir));
+  if (n_slices < 0 || (n_slices > 0 && !slices)) BCG_FAIL(c, BCG_ERR_INVALID, "bcg_basis_slice_triple: n_slices slices are needed");
+  const int Lg = c->gdims[dir], Ll = c->lat.L[dir], origin = c->lat.origin[dir];
+  const int S = n_slices > 0 ? n_slices : Lg;
+  // (local slice, index in the result) of the listed slices that are here, in ascending local slice
+  std::vector<int> list;
+  {
+    std::vector<int> index_of(Ll, -1);
+    std::vector<char> seen(Lg, 0);
+    for (int s = 0; s < S; ++s) {
+      const int t = n_slices > 0 ? slices[s] : s;
+      if (t < 0 || t >= Lg) BCG_FAIL(c, BCG_ERR_INVALID, "bcg_basis_slice_triple: slice outside the lattice");
+      if (seen[t]) BCG_FAIL(c, BCG_ERR_INVALID, "bcg_basis_slice_triple: a slice is listed twice");
+      seen[t] = 1;
+      if (t >= origin && t < origin + Ll) index_of[t - origin] = s;
+    }
+    for (int t = 0; t < Ll; ++t)
+      if (index_of[t] >= 0) {
+        list.push_back(t);
+        list.push_back(index_of[t]);
+      }
+  }
+  const int nl = static_cast<int>(list.size() / 2);
+  BCG_TRY(check_slice_momenta(c, who, dir, n_mom, momenta));
+  if (c->distributed && (!c->have_comm || !c->comm.allreduce_sum))
+    BCG_FAIL(c, BCG_ERR_COMM, "lattice is split over ranks but no bcg_comm was set");
+  for (int l = 0; l < 3; ++l)
+    if (K[l] > bcg::kTripleMaxColumns) BCG_FAIL(c, BCG_ERR_UNSUPPORTED, "bcg_basis_slice_triple: a list of more than 64 columns");
+  const int P = n_mom > 0 ? n_mom : 1;
+  const int64_t per = K[0] * K[1] * K[2];  // entries of one slice and momentum
+  if (per > kBasisSliceEntries / P / S)
+    BCG_FAIL(c, BCG_ERR_UNSUPPORTED, "bcg_basis_slice_triple: more than 2^26 entries; split the slices or the momenta");
+  const size_t entries = static_cast<size_t>(per) * P * S;
+  bool identical = na == nb && nb == nc;
+  for (int k = 0; identical && k < na; ++k) identical = A[k] == B[k] && B[k] == C[k];
+  std::vector<int> widths[3];
+  for (int l = 0; l < 3; ++l)
+    for (int k = 0; k < counts[l]; ++k) widths[l].push_back(lists[l][k]->m);
+  // whether a plan exists is decided for the most slices a rank can hold, so that every rank decides alike
+  bcg::BasisSliceTriplePlan plan;
+  for (const int n : {std::min(S, Ll), nl})
+    if (!bcg::basis_slice_triple_plan(widths[0].data(), na, widths[1].data(), nb, widths[2].data(), nc, identical, !c->force_generic, c->lat,
+                                      like->parity, dir, n, n_mom, &plan))
+      BCG_FAIL(c, BCG_ERR_UNSUPPORTED,
+               "bcg_basis_slice_triple: a slice of 2^30 rows or more, or too many listed slices for one block each; split the slices");
+  // c->dev_triple: [column table][tiles][slice list][phase tables of every momentum][block partials]
+  const auto in_entries = [](size_t bytes) { return (bytes + sizeof(double2) - 1) / sizeof(double2); };
+  const size_t col_entries = in_entries(3 * bcg::kTripleMaxColumns * sizeof(bcg::TripleCol));
+  const size_t tile_entries = in_entries(plan.tiles.size() * sizeof(int));
+  const size_t list_entries = in_entries(list.size() * sizeof(int));
+  const size_t per_tab = static_cast<size_t>(3) * plan.walk.ltab;
+  const size_t tab_entries = n_mom > 0 ? per_tab * P : 0;
+  const size_t head = col_entries + tile_entries + list_entries + tab_entries;
+  const size_t need = head + static_cast<size_t>(plan.partial_entries(nl));
+  int rc = ensure_basis(c, entries);
+  if (rc == BCG_OK && need > c->triple_entries) {
+    rc = stream_sync(c);
+    if (rc == BCG_OK) {
+      if (c->dev_triple) (void)hipFree(c->dev_triple);
+      c->dev_triple = nullptr;
+      c->triple_entries = 0;
+      if (hipMalloc(&c->dev_triple, need * sizeof(double2)) == hipSuccess) {
+        c->triple_entries = need;
+      } else {
+        c->dev_triple = nullptr;
+        c->err = "bcg_basis_slice_triple: hipMalloc of the block partials failed";
+        rc = BCG_ERR_HIP;
+      }
+    }
+  }
+  rc = agree_on_allocation(c, rc, who, "the result and the block partials");
+  if (rc != BCG_OK) {
+    if (c->distributed) release_basis(c);  // every rank starts the next call from the same state
+    return rc;
+  }
+  std::vector<double2> host(head, make_double2(0.0, 0.0));
+  {
+    bcg::TripleCol* cols = reinterpret_cast<bcg::TripleCol*>(host.data());
+    for (int l = 0; l < 3; ++l) {
+      int col = 0;
+      for (int k = 0; k < counts[l]; ++k)
+        for (int j = 0; j < lists[l][k]->m; ++j) cols[l * bcg::kTripleMaxColumns + col++] = bcg::TripleCol{lists[l][k]->d + j, lists[l][k]->m};
+    }
+    std::memcpy(host.data() + col_entries, plan.tiles.data(), plan.tiles.size() * sizeof(int));
+    if (nl > 0) std::memcpy(host.data() + col_entries + tile_entries, list.data(), list.size() * sizeof(int));
+    if (n_mom > 0) slice_phase_tables(c, plan.walk, momenta, P, 0, false, host.data() + col_entries + tile_entries + list_entries);
+  }
+  // the slices of other ranks, the slices nobody lists twice over and the entries the fold does not write: zeros
+  HIP_TRY(c, hipMemsetAsync(c->dev_basis, 0, entries * sizeof(double2), c->stream));
+  if (nl > 0) {
+    HIP_TRY(c, hipMemcpyAsync(c->dev_triple, host.data(), head * sizeof(double2), hipMemcpyHostToDevice, c->stream));
+    const bcg::TripleCol* const cols_dev = reinterpret_cast<const bcg::TripleCol*>(c->dev_triple);
+    const int* const tiles_dev = reinterpret_cast<const int*>(c->dev_triple + col_entries);
+    const int* const list_dev = reinterpret_cast<const int*>(c->dev_triple + col_entries + tile_entries);
+    const double2* const tabs_dev = c->dev_triple + col_entries + tile_entries + list_entries;
+    double2* const partials = c->dev_triple + head;
+    const double work = static_cast<double>(like->sites) / Ll * nl * plan.n_tiles();  // sites x tiles of a launch
+    for (int p = 0; p < P; ++p) {
+      {
+        ProfScope ps(c, "basis_slice_triple", work * 48.0 * 3.0 * plan.edge, work * 24.0 * static_cast<double>(plan.tile_entries()));
+        ProfScope form(c, plan.mfma ? "basis_slice_triple_form_mfma" : "basis_slice_triple_form_generic");
+        bcg::launch_basis_slice_triple(c->stream, c->lat, like->parity, dir, plan, nl, cols_dev, static_cast<int>(K[0]), static_cast<int>(K[1]),
+                                       static_cast<int>(K[2]), tiles_dev, list_dev, n_mom > 0 ? tabs_dev + p * per_tab : nullptr, partials);
+      }
+      BCG_TRY(check_launch(c, "basis_slice_triple"));
+      {
+        ProfScope ps(c, "basis_slice_triple_fold");
+        bcg::launch_basis_slice_triple_fold(c->stream, plan, nl, static_cast<int>(K[0]), static_cast<int>(K[1]), static_cast<int>(K[2]), S, p,
+                                            tiles_dev, list_dev, partials, c->dev_basis);
+      }
+      BCG_TRY(check_launch(c, "basis_slice_triple_fold"));
+    }
+  }
+  return download_basis(c, entries, out);
 }
 
 int bcg_field_copy_columns(bcg_field* dst, int dst_first, const bcg_field* src, int src_first, int n) {

@@ -453,6 +453,7 @@ int bcg_context_destroy(bcg_context* c) {
   if (c->dev_basis) (void)hipFree(c->dev_basis);
   if (c->pin_basis) (void)hipHostFree(c->pin_basis);
   if (c->basis_uploaded) (void)hipEventDestroy(c->basis_uploaded);
+  if (c->dev_triple) (void)hipFree(c->dev_triple);
   if (c->dev_rotate) (void)hipFree(c->dev_rotate);
   if (c->pin_rotate) (void)hipHostFree(c->pin_rotate);
   if (c->rotate_uploaded) (void)hipEventDestroy(c->rotate_uploaded);

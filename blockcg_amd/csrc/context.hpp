@@ -97,6 +97,8 @@ struct bcg_context {
   double* pin_basis = nullptr;           // pinned host copy
   size_t basis_entries = 0;              // complex entries either holds; grown on demand
   hipEvent_t basis_uploaded = nullptr;   // the last upload from pin_basis has left the host buffer
+  double2* dev_triple = nullptr;         // bcg_basis_slice_triple: column table, tiles, slice list, phase tables, block partials
+  size_t triple_entries = 0;             // double2 it holds; grown on demand
   double2* dev_rotate = nullptr;         // K x K matrix of bcg_basis_rotate, K <= 64 (capi_rotate.hip); allocated on first use
   double* pin_rotate = nullptr;          // pinned host copy
   size_t rotate_entries = 0;             // double2 in either: 64 x 64, grown by bcg_basis_slice_rotate (one matrix per slice)

@@ -155,4 +155,45 @@ bool basis_slice_axpy_plan(const LatticeDev& lat, int parity, int dir, int n_sli
   return true;
 }
 
+bool basis_slice_triple_plan(const int* wa, int na, const int* wb, int nb, const int* wc, int nc, bool identical, bool fast,
+                             const LatticeDev& lat, int parity, int dir, int n_slices, int n_mom, BasisSliceTriplePlan* plan) {
+  (void)n_mom;  // one momentum per launch whatever their number
+  const int* w[3] = {wa, wb, wc};
+  const int n[3] = {na, nb, nc};
+  int K[3] = {0, 0, 0};
+  bool mfma = fast;
+  for (int l = 0; l < 3; ++l)
+    for (int k = 0; k < n[l]; ++k) {
+      K[l] += w[l][k];
+      mfma = mfma && basis_mfma_width(w[l][k]);
+      if (K[l] > kTripleMaxColumns) return false;
+    }
+  plan->mfma = mfma;
+  plan->identical = identical;
+  plan->edge = mfma ? kTripleEdgeMfma : kTripleEdgeGeneric;
+  plan->pc = 1;
+  int nt[3];
+  for (int l = 0; l < 3; ++l) nt[l] = (K[l] + plan->edge - 1) / plan->edge;
+  plan->tiles.clear();
+  for (int ta = 0; ta < nt[0]; ++ta)
+    for (int tb = identical ? ta : 0; tb < nt[1]; ++tb)
+      for (int tc = identical ? tb : 0; tc < nt[2]; ++tc) {
+        plan->tiles.push_back(ta);
+        plan->tiles.push_back(tb);
+        plan->tiles.push_back(tc);
+      }
+  int64_t n_virtual;
+  if (!slice_walk_begin(lat, parity, dir, &plan->walk, &n_virtual)) return false;
+  const int64_t per_slice = static_cast<int64_t>(n_slices > 0 ? n_slices : 1) * plan->n_tiles();  // blocks at nbps = 1
+  const int64_t room = kTriplePartialEntries / plan->tile_entries();
+  if (per_slice > room) return false;
+  const int64_t most = (n_virtual + kTripleChunkRows - 1) / kTripleChunkRows;
+  int64_t nbps = std::min<int64_t>(std::min<int64_t>(std::max<int64_t>(kTripleBlocks / per_slice, 1), room / per_slice), most);
+  if (nbps < 1) nbps = 1;
+  const int64_t chunk = ((n_virtual + nbps - 1) / nbps + kTripleChunkRows - 1) / kTripleChunkRows * kTripleChunkRows;
+  plan->walk.chunk = static_cast<int>(chunk);
+  plan->walk.nbps = static_cast<int>((n_virtual + chunk - 1) / chunk);
+  return true;
+}
+
 }  // namespace bcg

@@ -87,4 +87,36 @@ constexpr int kBasisSliceAxpyBlocks = 2048;  // the grid aimed at, as in the per
 // n_slices: the local slices the launch walks (>= 1).  Returns false when a slice has 2^30 rows or more.
 bool basis_slice_axpy_plan(const LatticeDev& lat, int parity, int dir, int n_slices, SliceWalk* plan);
 
+// ---- bcg_basis_slice_triple (kernels_basis_slice_triple.hpp) ----------------------------------------
+// A block owns one output tile of edge^3 entries (edge columns of each list) on one chunk of one listed slice.  The walk
+// differs from the other plans' in its unit: a step is four whole sites (12 rows: three k-steps of the matrix instruction,
+// or one colour triple per site), and the chunk is a whole number of 16-site rounds (48 rows, which is also a multiple of
+// the 16 rows every SliceWalk keeps).
+constexpr int kTripleMaxColumns = 64;             // total width of a list
+constexpr int kTripleEdgeMfma = 16;               // tile edge of the MFMA form
+constexpr int kTripleEdgeGeneric = 8;             // and of the generic form
+constexpr int kTripleChunkRows = 48;              // the chunk is a multiple of it
+constexpr int kTripleBlocks = 1024;               // the grid aimed at: two blocks per CU, twice over
+constexpr int64_t kTriplePartialEntries = int64_t(1) << 24;  // block partials of one launch at the most (256 MiB)
+
+struct BasisSliceTriplePlan {
+  bool mfma;               // every width of the three lists in {16, 32} and the MFMA form allowed
+  bool identical;          // the three lists are one list: only tiles ta <= tb <= tc
+  int edge;                // tile edge
+  int pc;                  // momenta per launch: 1 (the accumulators of one momentum fill the MFMA form's budget)
+  SliceWalk walk;          // nbps: blocks per (slice, tile)
+  std::vector<int> tiles;  // (ta, tb, tc) per tile, in ascending (ta, tb, tc): columns edge * t .. of each list
+  int n_tiles() const { return static_cast<int>(tiles.size() / 3); }
+  int64_t tile_entries() const { return static_cast<int64_t>(edge) * edge * edge; }
+  // block partials of one launch over n_slices local slices
+  int64_t partial_entries(int n_slices) const { return static_cast<int64_t>(n_slices) * n_tiles() * walk.nbps * tile_entries(); }
+};
+
+// widths of the three lists; identical: they are the same list; fast: bcg_force_generic not set; n_slices: the listed
+// slices that are local (>= 0; 0 plans as for one).  A pure function of its arguments.  Returns false when a list is
+// wider than kTripleMaxColumns, a slice has 2^30 rows or more, or one block per (slice, tile) already needs more than
+// kTriplePartialEntries of partials (the caller lists fewer slices).
+bool basis_slice_triple_plan(const int* wa, int na, const int* wb, int nb, const int* wc, int nc, bool identical, bool fast,
+                             const LatticeDev& lat, int parity, int dir, int n_slices, int n_mom, BasisSliceTriplePlan* plan);
+
 }  // namespace bcg

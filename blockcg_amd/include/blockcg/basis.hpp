@@ -1,5 +1,6 @@
 // blockcg/basis.hpp -- products between a solve block and a basis of another width, and deflation on top of them
-// (include/blockcg_hip.h: bcg_basis_dot, bcg_basis_axpy, bcg_basis_slice_dot, bcg_basis_slice_axpy, bcg_field_copy_columns).
+// (include/blockcg_hip.h: bcg_basis_dot, bcg_basis_axpy, bcg_basis_slice_dot, bcg_basis_slice_axpy, bcg_basis_slice_triple,
+// bcg_field_copy_columns).
 //
 //   basis V;  V.push_back(f)                     a list of fields of any widths 1 .. 32; K = the sum of the widths
 //   basis_dot(V, b)                              C = V^dagger b, K x m column-major (element (i, j) at j * K + i)
@@ -7,6 +8,7 @@
 //   basis_slice_dot(V, b, dir[, momenta])        V^dagger b by slice of dir (and momentum): L_dir matrices K x m per momentum
 //   basis_slice_axpy(y, V, dir, slices, C, momentum, beta)   its adjoint: y <- beta y + w V C[s] on the listed slices
 //   distillation_source(y, V, dir, t0, first)    y = columns first .. of V on the slice t0, zero elsewhere
+//   basis_slice_triple(A, B, C, dir, slices, momenta)   baryon elementals: sum over a slice of det[A_i(x), B_j(x), C_k(x)]
 //   copy_columns(dst, dst_first, src, src_first, n)   n columns between fields of different widths
 //   deflate(B, V)                                B <- B - V (V^dagger B); returns C = V^dagger B
 //   low_mode_solution(X, V, evals, C, sigma)     X_s += V (Lambda + sigma_s)^-1 C
@@ -151,6 +153,34 @@ void distillation_source(block_fermion_field<N_rhs>& y, const basis& V, int dir,
   std::vector<basis_matrix> C(1, basis_matrix(static_cast<size_t>(V.K()) * N_rhs));
   for (int j = 0; j < N_rhs; ++j) C[0][static_cast<size_t>(j) * V.K() + first + j] = 1.0;
   basis_slice_axpy(y, V, dir, std::vector<int>(1, t0), C, std::vector<int>(), 0.0);
+}
+
+// Baryon elementals (bcg_basis_slice_triple): entry p * S + s of the result is the Ka x Kb x Kc tensor
+// T_p(s)(i, j, k) = sum_{x_dir = slices[s]} w_p(x) det[A_i(x), B_j(x), C_k(x)], element (i, j, k) at (k * Kb + j) * Ka + i.
+// slices empty: all L_dir slices in ascending order (S = L_dir); momenta empty: the single momentum 0, no phase arithmetic.
+// The same basis three times gives a result that is antisymmetric bit for bit.
+inline std::vector<basis_matrix> basis_slice_triple(const basis& A, const basis& B, const basis& C, int dir,
+                                                    const std::vector<int>& slices = std::vector<int>(),
+                                                    const std::vector<std::vector<int>>& momenta = std::vector<std::vector<int>>()) {
+  if (dir < 0 || dir >= static_cast<int>(A.lat().dims().size())) throw std::runtime_error("basis_slice_triple: direction outside the lattice");
+  std::vector<int> n(4 * momenta.size(), 0);
+  for (size_t p = 0; p < momenta.size(); ++p) {
+    if (momenta[p].size() > 4) throw std::runtime_error("basis_slice_triple: a momentum has up to 4 components");
+    for (size_t mu = 0; mu < momenta[p].size(); ++mu) n[4 * p + mu] = momenta[p][mu];
+  }
+  A.flush();
+  B.flush();
+  C.flush();
+  const size_t S = slices.empty() ? static_cast<size_t>(A.lat().dims()[dir]) : slices.size();
+  const size_t P = momenta.empty() ? 1 : momenta.size(), E = static_cast<size_t>(A.K()) * B.K() * C.K();
+  std::vector<std::complex<double>> buf(P * S * E);
+  check(bcg_basis_slice_triple(A.handles(), A.size(), B.handles(), B.size(), C.handles(), C.size(), dir, static_cast<int>(slices.size()),
+                               slices.empty() ? nullptr : slices.data(), static_cast<int>(momenta.size()), momenta.empty() ? nullptr : n.data(),
+                               reinterpret_cast<double*>(buf.data())),
+        A.lat().ctx(), "basis_slice_triple");
+  std::vector<basis_matrix> out(P * S);
+  for (size_t k = 0; k < P * S; ++k) out[k].assign(buf.begin() + k * E, buf.begin() + (k + 1) * E);
+  return out;
 }
 
 template <int N_dst, int N_src>

@@ -476,12 +476,38 @@ int bcg_covariant_smear(bcg_context* ctx, const bcg_gauge* g, bcg_field* f, bcg_
  *    y among the V_k, a non-finite beta -- and dir outside 0 .. ndim-1, n_slices < 0, n_slices > 0 with slices == NULL, a
  *    slice outside 0 .. L_dir-1 or listed twice, a non-zero momentum component along dir or along a direction >= ndim.
  *    BCG_ERR_UNSUPPORTED: more than 2^26 entries of C, or a slice of 2^30 rows or more.  All are returned before the first
- *    launch and leave y exactly as it was. */
+ *    launch and leave y exactly as it was.
+ *
+ * bcg_basis_slice_triple: the baryon elementals of three lists of fields, slice by slice,
+ *   out[(((p*S + s)*Kc + k)*Kb + j)*Ka + i] = sum_{x: x_dir = slices[s]} w_p(x) sum_{abc} eps_abc A_i(x,a) B_j(x,b) C_k(x,c),
+ * interleaved (re, im): the colour determinant of three columns summed over a slice.  A, B, C: lists as V above (widths
+ * 1 .. 32, columns numbered through the list), Ka, Kb, Kc <= 64 columns each, all fields of one context, parity and site
+ * count; the lists may share fields or be the same list.  dir, n_slices, slices as in bcg_basis_slice_axpy (distinct GLOBAL
+ * indices in any order; n_slices = 0: all L_dir slices ascending, S = L_dir); only the listed slices are walked.  n_mom,
+ * momenta, w_p and the host phase tables exactly as in bcg_basis_slice_dot.  Nothing is written but out.
+ * A launch is one momentum; a block owns one tile of the result (16^3 entries in the MFMA form: every width of the three
+ * lists in {16, 32} and bcg_force_generic not set; 8^3 in the generic form) on a chunk of one slice, forms the cross product
+ * A_i x B_j of a site in registers and contracts it with w C_k.  Identical lists (na == nb == nc and the same handles element
+ * by element): only tiles in ascending order are launched, only the entries i < j < k are kept and each is written with its
+ * five signed images, so out is antisymmetric bit for bit and exactly 0 where two indices coincide.  No atomics: the plan is
+ * fixed by shape, widths, parity, dir, the listed slices and n_mom, and the block partials of a (p, s, tile) are added in
+ * ascending order: the same bits on every call.  The result is assembled on the device, summed over ranks with ONE
+ * bcg_comm.allreduce_sum and copied out once, identical on every rank.  Synchronizes the stream.
+ *  - Profile keys "basis_slice_triple" (48 * 3 * edge bytes and 24 * edge^3 flops per listed site, tile and launch),
+ *    "basis_slice_triple_fold", "basis_slice_triple_form_mfma" / "basis_slice_triple_form_generic" (launch counts).
+ *  - BCG_ERR_INVALID: everything bcg_basis_dot rejects about a list (NULL, n < 1, mixed contexts, parities or site counts),
+ *    everything bcg_basis_slice_axpy rejects about dir and slices, everything bcg_basis_slice_dot rejects about momenta, a
+ *    NULL out.  BCG_ERR_COMM: a divided lattice without a bcg_comm.  BCG_ERR_UNSUPPORTED: a list of more than 64 columns,
+ *    more than 2^26 entries in all (split the slices or the momenta), a slice of 2^30 rows or more, or so many listed slices
+ *    that one block per (slice, tile) exceeds 2^24 entries of block partials.  All are returned before the first launch and
+ *    leave out untouched. */
 int bcg_basis_dot(const bcg_field* const* V, int nv, const bcg_field* b, double* out);
 int bcg_basis_slice_dot(const bcg_field* const* V, int nv, const bcg_field* b, int dir, int n_mom, const int* momenta, double* out);
 int bcg_basis_axpy(bcg_field* y, const bcg_field* const* V, int nv, const double* C, double beta);
 int bcg_basis_slice_axpy(bcg_field* y, const bcg_field* const* V, int nv, int dir, int n_slices, const int* slices, const double* C,
                          const int* momentum, double beta);
+int bcg_basis_slice_triple(const bcg_field* const* A, int na, const bcg_field* const* B, int nb, const bcg_field* const* C, int nc, int dir,
+                           int n_slices, const int* slices, int n_mom, const int* momenta, double* out);
 int bcg_field_copy_columns(bcg_field* dst, int dst_first, const bcg_field* src, int src_first, int n);
 
 /* ---- low modes: the in-place basis rotation and the eigensolver built on it (extensions) ----------
