@@ -48,6 +48,15 @@ __device__ __forceinline__ unsigned lds_addr_of(const void* p) {
 #ifndef BCG_HOP4B_BCAST
 #define BCG_HOP4B_BCAST 1
 #endif
+// Q_AHEAD (k_hop4b_fusedB): the Q rows of step x3 + 1 are loaded in the tail of step x3 and carried over the loop's back edge
+// like the rows that leave the bundle, so that the product Q rho_prev^-1 -- 12 of the tail's 30 matrix instructions, which
+// need nothing from the stencil -- leaves the tail (it stands behind direction 1) and the issue of the Q loads, a third of a
+// vector-memory phase that every wave of the block waited out, runs beside the tail's matrix instructions instead -- see
+// "Q_AHEAD" in hop4b_body; measured in profiles/r11_fused_q_ahead_ab.txt.  -DBCG_FUSEB_Q_AHEAD=0 (A/B build): Q loaded in the
+// step that uses it and the whole of phase B in the tail, the parent's device code.
+#ifndef BCG_FUSEB_Q_AHEAD
+#define BCG_FUSEB_Q_AHEAD 1
+#endif
 __device__ __forceinline__ void glds16_link(const void* gsrc, unsigned lds_dst) {
   unsigned keep;
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
@@ -956,6 +965,7 @@ __device__ __forceinline__ void hop4b_body(const LatticeDev& lat, const double2*
   //   SHIFT  -- the epilogue has a c0 term (from `p`, or from the own row).
   // FUSEB (HOP_FACT2B): the second factor with phase B of the solver in its tail -- see "FUSEB" in the pipelined step.
   constexpr bool FUSEB = MODE == HOP_FACT2B;
+  constexpr bool Q_AHEAD = FUSEB && BCG_FUSEB_Q_AHEAD != 0;
   constexpr bool FACT = MODE == HOP_FACT1 || MODE == HOP_FACT2 || FUSEB;
   constexpr bool PLUS_D = MODE == HOP_FACT2 || FUSEB;  // c0 in + D in (the other shifted forms: c0 p - D in)
   constexpr bool HAS_P = MODE == HOP_SHIFTED || MODE == HOP_RESID;
@@ -1504,6 +1514,18 @@ __device__ __forceinline__ void hop4b_body(const LatticeDev& lat, const double2*
 #pragma unroll
         for (int s = 0; s < 4; ++s) qo[s] = has_rinv ? qa0 + s * 64 : voff + (s < 3 ? s : 2) * M * 16;
       }
+      // Q_AHEAD: the wave's Q rows of the step at hand, carried from step to step like q1 / q2: loaded here for a column's first
+      // step, in the tail of step x3 for step x3 + 1 (group q, retired with n1 / n2 behind the end-of-step wait).  ip_p then runs one
+      // row ahead of the step.  Writing Q' over Q stays legal: a row of Q is read by one wave only, the one that owns its
+      // sites, in the step before the one whose tail writes that row (here: in front of the column's first step) -- the read
+      // is retired before the wave enters the step that stores to the row, and no other wave ever stores there.
+      dv2 qc[4];
+      if constexpr (Q_AHEAD) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) qc[s] = *reinterpret_cast<const dv2*>(ip_p + qo[s]);
+        asm volatile("" : "+v"(qc[0]), "+v"(qc[1]), "+v"(qc[2]), "+v"(qc[3]));  // retired here, like q1 / q2
+        ip_p += id_row;
+      }
       // link DMAs of this wave (checkerboard form: the forward links and all four directions' backward links, every wave)
       const int nC = CB ? RFW + 4 * RBK : RFW + 1 + (e1 ? 0 : RBK) + (e2 ? 0 : RBK);
       constexpr int nD = 6, nS = 3;
@@ -1599,11 +1621,15 @@ __device__ __forceinline__ void hop4b_body(const LatticeDev& lat, const double2*
           b0[c] = Cown[co + (CB ? rr - 1 : -1) * 3 * M + c * M];
         }
         // factored pair: the lane's own site, from the same slot (nothing writes it during the step: the +x3 DMA goes to Cn)
+        // (Q_AHEAD: read in the tail, where it is used -- nothing writes the own sites of this slot during the step, the exchange
+        //  of T in the tail takes the slot's halo sites -- so that the product's accumulators fit the register file)
         dv2 own[3];
-        if (FACT) {
+        if (FACT && !Q_AHEAD) {
 #pragma unroll
           for (int c = 0; c < 3; ++c) own[c] = Cown[co + c * M];
         }
+        dv2 cdq = dv2{0.0, 0.0};  // Q_AHEAD: rho_prev^-1, the B operand of the product's next k-step
+        if constexpr (Q_AHEAD) cdq = Mr[lane];
         const int64_t crow_site = static_cast<int64_t>(col) + static_cast<int64_t>(x3) * S3;
         const char* const prow = INCR ? ip_p : reinterpret_cast<const char*>(p) + crow_site * RB;
         char* const orow = INCR_OUT ? ip_o : reinterpret_cast<char*>(out) + (RING_OUT ? static_cast<int64_t>(col) + static_cast<int64_t>(slot) * S3 : crow_site) * RB;
@@ -1724,7 +1750,7 @@ __device__ __forceinline__ void hop4b_body(const LatticeDev& lat, const double2*
           asm volatile("; ASYNC_ISSUED p");
         }
         dv2 qv[4];
-        if (FUSEB) {
+        if (FUSEB && !Q_AHEAD) {
           asm volatile("; ASYNC_ISSUE q");
           qv[0] = ld_sv_async<0>(prow, qo[0]);
           qv[1] = ld_sv_async<0>(prow, qo[1]);
@@ -1796,8 +1822,52 @@ __device__ __forceinline__ void hop4b_body(const LatticeDev& lat, const double2*
     N[2] = ld_sv_async<2 * M * 16>(A, voff);             \
     asm volatile("; ASYNC_ISSUED " TAG);                 \
   }
+        // Q_AHEAD: (Q rho_prev^-1) of THIS step from the carried rows, here instead of in the tail -- the first call of the tail's
+        // rmul_rows (below) operation for operation, on the same operands in the same order: K from zero, four k-steps of three
+        // matrix instructions, folded last; without rho_prev^-1 the plain copy.  The tail continues on (ARq, AIq) with T alpha.
+        // The k-steps stand between the two groups of next-row loads (which need no register of theirs); the coefficients are
+        // read from LDS a k-step ahead.  Where in the step the product stands hardly matters (measured: behind direction 0
+        // between the link DMAs, there in front of them, and here -- profiles/r11_fused_q_ahead_ab.txt); this place needs the
+        // fewest registers.
+        vd4 ARq = vd4{0.0, 0.0, 0.0, 0.0}, AIq = vd4{0.0, 0.0, 0.0, 0.0}, Kq = vd4{0.0, 0.0, 0.0, 0.0};
+        auto rinv_kstep = [&](int s) __attribute__((always_inline)) {
+          if constexpr (Q_AHEAD) {
+            __builtin_amdgcn_sched_barrier(0);
+            const dv2 cd = cdq;  // (without rho_prev^-1 that half of the matrices' LDS holds nothing: read, not used)
+            if (s < 3) cdq = Mr[64 * (s + 1) + lane];
+            if (has_rinv) {
+              if constexpr (kGauss3M<16>) {
+                Kq = mfma(qc[s].x + qc[s].y, cd.x, Kq);
+                ARq = mfma_nega(qc[s].y, cd.x + cd.y, ARq);
+                AIq = mfma(qc[s].x, cd.y - cd.x, AIq);
+              } else {
+                ARq = mfma(qc[s].x, cd.x, ARq);
+                ARq = mfma_nega(qc[s].y, cd.y, ARq);
+                AIq = mfma(qc[s].x, cd.y, AIq);
+                AIq = mfma(qc[s].y, cd.x, AIq);
+              }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        };
+        if constexpr (Q_AHEAD) {
+          rinv_kstep(0);
+          BCG_NEXT_ROW("n1", n1, a_n1)
+          rinv_kstep(1);
+          BCG_NEXT_ROW("n2", n2, a_n2)
+          rinv_kstep(2);
+          rinv_kstep(3);
+          if (!has_rinv) {  // (fourth entry: the repeated load -- a row of the tile that is never looked at, but a defined value)
+            ARq = vd4{qc[0].x, qc[1].x, qc[2].x, qc[3].x};
+            AIq = vd4{qc[0].y, qc[1].y, qc[2].y, qc[3].y};
+          }
+          if constexpr (kGauss3M<16>) {
+            if (has_rinv) rmul_gauss_fold(ARq, AIq, Kq);
+          }
+        } else {
         BCG_NEXT_ROW("n1", n1, a_n1)
         if (!SP_D) { BCG_NEXT_ROW("n2", n2, a_n2) }
+        }
         __builtin_amdgcn_sched_barrier(0);
         BCG_STAMPB(6)   // next rows issued
 #define BCG_C3 if (C_PIECES) { BCG_LINK_PIECE(2) }
@@ -1814,7 +1884,8 @@ __device__ __forceinline__ void hop4b_body(const LatticeDev& lat, const double2*
 #undef BCG_NEXT_ROW
         BCG_STAMPB(7)   // direction 2
         // ---- the +x3 row has landed in Cn once at most E, C and D (and the touches) are outstanding
-        wait_vmcnt(nE + (more ? nC + nD : 0));
+        // (Q_AHEAD: group q is issued in the tail, behind this wait -- counted here, the +x3 row would be read before it has landed)
+        wait_vmcnt((Q_AHEAD ? 0 : nE) + (more ? nC + nD : 0));
         BCG_STAMPB(8)   // wait for the +x3 row
 #pragma unroll
         for (int c = 0; c < 3; ++c) f3[c] = Cn[co + c * M];
@@ -1845,6 +1916,10 @@ __device__ __forceinline__ void hop4b_body(const LatticeDev& lat, const double2*
           pw[0] = make_double2(r0.x, r0.y);
           pw[1] = make_double2(r1.x, r1.y);
           pw[2] = make_double2(r2.x, r2.y);
+        }
+        if (Q_AHEAD) {
+#pragma unroll
+          for (int c = 0; c < 3; ++c) own[c] = Cown[co + c * M];
         }
         if (FACT) {
 #pragma unroll
@@ -1880,8 +1955,25 @@ __device__ __forceinline__ void hop4b_body(const LatticeDev& lat, const double2*
           dv2* const tw = chunk(sw);
 #pragma unroll
           for (int c = 0; c < 3; ++c) tw[c * M + j] = dv2{tv[c].x, tv[c].y};
-          wait_vmcnt(more ? nC + nD : 0);  // Q
+          if constexpr (!Q_AHEAD) wait_vmcnt(more ? nC + nD : 0);  // Q
+          // Q_AHEAD: the rows of step x3 + 1 (prow: ip_p runs a row ahead), issued here, where the carried rows are dead, straight
+          // into their registers: there is no second set to load into -- 16 registers the kernel does not have -- and so no
+          // copy at the retire; the build's check of the device code sees to it that nothing names them up to the
+          // end-of-step wait.  One offset register and wave-uniform strides (qo: four registers held along the whole sweep).
+          // Their issue runs beside the matrix instructions of the tail.
+          if constexpr (Q_AHEAD) {
+            if (more) {
+              const int st1 = has_rinv ? 64 : M * 16, st2 = 2 * st1, st3 = has_rinv ? 3 * 64 : 2 * M * 16;
+              asm volatile("; ASYNC_ISSUE q");
+              qc[0] = ld_sv_async<0>(prow, qo[0]);
+              qc[1] = ld_sv_async<0>(prow + st1, qo[0]);
+              qc[2] = ld_sv_async<0>(prow + st2, qo[0]);
+              qc[3] = ld_sv_async<0>(prow + st3, qo[0]);
+              asm volatile("; ASYNC_ISSUED q");
+            }
+          }
           dv2 qw[4];
+          if constexpr (!Q_AHEAD)
           asm volatile("; ASYNC_RETIRE q\n\tv_mov_b64 %0, %8\n\tv_mov_b64 %1, %9\n\tv_mov_b64 %2, %10\n\tv_mov_b64 %3, %11\n\t"
                        "v_mov_b64 %4, %12\n\tv_mov_b64 %5, %13\n\tv_mov_b64 %6, %14\n\tv_mov_b64 %7, %15"
                        : "=&v"(qw[0].x), "=&v"(qw[0].y), "=&v"(qw[1].x), "=&v"(qw[1].y), "=&v"(qw[2].x), "=&v"(qw[2].y),
@@ -1916,7 +2008,10 @@ __device__ __forceinline__ void hop4b_body(const LatticeDev& lat, const double2*
             }
           };
           vd4 AR = vd4{0.0, 0.0, 0.0, 0.0}, AI = vd4{0.0, 0.0, 0.0, 0.0};
-          if (has_rinv) {
+          if constexpr (Q_AHEAD) {  // formed behind direction 1
+            AR = ARq;
+            AI = AIq;
+          } else if (has_rinv) {
             rmul_rows(AR, AI, qw, Mr);
           } else {  // (fourth entry: the repeated load -- a row of the tile that is never looked at, but a defined value)
             AR = vd4{qw[0].x, qw[1].x, qw[2].x, qw[3].x};
@@ -1947,6 +2042,10 @@ __device__ __forceinline__ void hop4b_body(const LatticeDev& lat, const double2*
         BCG_STAMPB(10)  // U_3 carried, wait for p, output, stores
         // everything but the stores: the links and the next rows have landed before this wave reaches the barrier
         __builtin_amdgcn_sched_barrier(0);
+        // (Q_AHEAD: the wait once more in front of the branch, on every path.  hipcc lays the two sides below out as two skips
+        //  in a row, and the check of the device code, which does not know that one of them is always taken, would walk past
+        //  both waits and round the loop into the next step's product, which reads the carried registers.)
+        if constexpr (Q_AHEAD) asm volatile("s_waitcnt vmcnt(%0)" : : "n"(nS) : "memory");
         if (more) {
           asm volatile("s_waitcnt vmcnt(%24) ; ASYNC_RETIRE n1 ASYNC_RETIRE n2\n\t"
                        "v_mov_b64 %0, %12\n\tv_mov_b64 %1, %13\n\tv_mov_b64 %2, %14\n\tv_mov_b64 %3, %15\n\tv_mov_b64 %4, %16\n\tv_mov_b64 %5, %17\n\t"
@@ -1956,6 +2055,8 @@ __device__ __forceinline__ void hop4b_body(const LatticeDev& lat, const double2*
                        : "v"(n1[0].x), "v"(n1[0].y), "v"(n1[1].x), "v"(n1[1].y), "v"(n1[2].x), "v"(n1[2].y),
                          "v"(n2[0].x), "v"(n2[0].y), "v"(n2[1].x), "v"(n2[1].y), "v"(n2[2].x), "v"(n2[2].y), "n"(nS)
                        : "memory");
+          if constexpr (Q_AHEAD)  // behind the same wait: the carried Q rows are the registers they were loaded into
+            asm volatile("; ASYNC_RETIRE q" : "+v"(qc[0]), "+v"(qc[1]), "+v"(qc[2]), "+v"(qc[3]));
         } else {
           asm volatile("s_waitcnt vmcnt(%0)" : : "n"(nS) : "memory");
         }

@@ -15,11 +15,17 @@ under `!more`, so for each of them exactly two statically infeasible paths exist
 through the `!more` side of the step's tail, one that leaves the loop behind the issue and runs to s_endpgm.  Those two
 (at most one of each kind, groups n1 and n2 only) are reported and tolerated; any further lost path, a lost path of another
 group, or a jump table fails the build (tests/test_build_checks.py feeds a synthetic loop-without-retire listing).
+Group q (the Q rows of the fused phase B) crosses the loop's back edge as n1 / n2 do (BCG_FUSEB_Q_AHEAD): the rows of step
+x3 + 1 are issued under `more` in the tail of step x3, straight into the registers that carry them -- there is no copy at the
+retire -- and the next step's product READS those registers, so a lost path round the loop would show as a violation.  It is
+not on the allow-list and needs no place there: that kernel repeats the end-of-step wait in front of the `more` branch, on
+every path, and the walk of every group ends at it.  Inside a group's bracket nothing but its loads may name a destination
+register either (the loads of a group may have other instructions between them).
 
 The instantiations are found by name (every `k_hop4b...` function of the listing), so new ones are covered as they are
 added: the first factor with its Gram product (`k_hop4b<16, HOP_FACT1, true>`: the groups n1 / n2 of the plain form) and the
-second factor fused with phase B (`k_hop4b_fusedB`), whose Q rows travel in the group `q` -- issued in p's place, retired in
-the tail.  A listing that holds `k_hop4b_fusedB` without a group `q` fails: the loads would have become visible to hipcc or
+second factor fused with phase B (`k_hop4b_fusedB`), whose Q rows travel in the group `q` -- issued in p's place and retired
+in the tail, or a step ahead (above).  A listing that holds `k_hop4b_fusedB` without a group `q` fails: the loads would have become visible to hipcc or
 lost their markers.
 
 usage: tools/check_async_regs.py <device asm from `hipcc -S --cuda-device-only`>   exit status 1 on a violation
@@ -53,13 +59,18 @@ def main(path):
             seen += 1
             j = i + 1
             regs = set()
+            inside = []
             while j < len(lines) and f'ASYNC_ISSUED {tag}' not in lines[j]:
                 d = re.search(r'global_load_dwordx4\s+([va])\[(\d+):(\d+)\]', lines[j])
                 if d:
                     base = 1000 if d.group(1) == 'a' else 0
                     regs |= set(range(base + int(d.group(2)), base + int(d.group(3)) + 1))
+                else:  # inside the bracket: an instruction between two loads of the group must not name a register already in flight
+                    l = lines[j].split(';')[0].strip()
+                    if l and not l.startswith('.') and not l.endswith(':') and regs_of(l) & regs:
+                        inside.append((j, lines[j].strip()))
                 j += 1
-            todo, done, bad, reached, lost = [j + 1], set(), [], 0, 0
+            todo, done, bad, reached, lost = [j + 1], set(), list(inside), 0, 0
             why = []
             walked = 0
             while todo:

@@ -5,7 +5,10 @@ k_hop4c: library built with -DBCG_HOP4C_STAMPS and BCG_HOP_BUNDLE=0; k_hop4b (th
 segments of the software-pipelined step; `fact2`: the second pass of the factored pair (HOP_FACT2, with its Gram product) of the
 solver's phase A instead of the plain hop, which leaves its stamps behind the Gram partials -- with BCG_HOP_FUSED_B=0; with the
 default (1) both factors carry a Gram product and stamp the same place, so what is read is the later launch: the second
-factor fused with phase B (k_hop4b_fusedB), whose segment "carry U3, WAIT p, output, stores" holds phase B's products."""
+factor fused with phase B (k_hop4b_fusedB), whose segment "carry U3, WAIT p, output, stores" holds phase B's products.
+`fusedb`: that launch under its own segment names (one SBCGrQ iteration, the stamps of its later launch); `fact1g`: the first
+factor with its Gram product alone (k_hop4b<16, HOP_FACT1, GRAM>, through the test aid bcg_debug_fused_first_factor, so that
+the fused launch does not overwrite its stamps)."""
 import ctypes
 import os
 import sys
@@ -26,14 +29,20 @@ st.iterate(1)  # allocates the scratch buffer
 mode = sys.argv[1] if len(sys.argv) > 1 else ""
 y = bc.block_fermion_field(ctx, m)
 for _ in range(3):
-    if mode == "fact2":
+    if mode in ("fact2", "fusedb"):
         st.iterate(1)
+    elif mode == "fact1g":
+        ff = ctx.lib.bcg_debug_fused_first_factor
+        ff.restype = ctypes.c_int
+        ff.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]
+        ctx.check(ff(ctx.h, D.h, D.mass, 0.0, y.h, B.h))
     else:
         D.D(y, B)
 ctx.synchronize()
 nblk = 512
-NSEG = 16 if mode in ("4b", "pipe", "fact2") else 8
-skip = 1024 * m * m * 2 if mode == "fact2" else 0  # doubles: the Gram partials of the largest grid (kHopStampsSkipBlocks, kernels_mfma.hpp)
+GRAM_MODES = ("fact2", "fusedb", "fact1g")  # launches with a Gram product: the stamps lie behind its partials
+NSEG = 16 if mode in ("4b", "pipe") + GRAM_MODES else 8
+skip = 1024 * m * m * 2 if mode in GRAM_MODES else 0  # doubles: the Gram partials of the largest grid (kHopStampsSkipBlocks, kernels_mfma.hpp)
 buf = np.zeros(skip + nblk * 4 * NSEG, dtype=np.float64)
 lib = ctx.lib
 lib.bcg_debug_read_scratch.restype = ctypes.c_int
@@ -44,9 +53,13 @@ tiles = 64 ** 4 // 16 // nblk
 names = ["park+pace", "barrier", "issue(links,dir0)", "dir0", "dir1", "dir2", "dir3(+x3)", "tail(p,store)"]
 if len(sys.argv) > 1 and sys.argv[1] == "4b":
     names = ["pace(thread 0)", "barrier", "issue(DMAs,loads)", "dir0 (LDS only)", "dir1 (+wait loads)", "dir2", "dir3", "tail(park,store)"]
-if mode in ("pipe", "fact2"):  # the software-pipelined step (PIPE in hop4b_body)
+if mode in ("pipe", "fact2", "fact1g"):  # the software-pipelined step (PIPE in hop4b_body)
     names = ["loop overhead", "barrier", "-x3 readback + row DMAs", "dir0", "issue p + link DMAs", "dir1", "issue next rows", "dir2",
              "WAIT +x3 row", "dir3", "carry U3, WAIT p, output, stores", "WAIT links + next rows"]
+if mode == "fusedb":  # the same step with the Q rows in p's place and phase B in the tail
+    names = ["loop overhead", "barrier", "-x3 readback + row DMAs", "dir0", "issue Q + link DMAs", "dir1",
+             "Q rho_prev^-1 (if ahead) + issue next rows", "dir2", "WAIT +x3 row", "dir3",
+             "carry U3, T exchange, phase B, stores, Gram", "WAIT links + next rows (+ next Q)"]
 tot = seg.sum(axis=2)
 print("cycles per tile per wave (s_memtime ticks = shader cycles): total median %.0f" % np.median(tot / tiles))
 for i, n in enumerate(names):
