@@ -128,6 +128,9 @@ SIGNATURES = {
                                            c_dbl_p, ctypes.c_int]),
     "bcg_covariant_smear": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                            ctypes.c_double, ctypes.c_int]),
+    "bcg_gauge_stout_smear": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_dbl_p, ctypes.c_int,
+                                             ctypes.c_void_p]),
+    "bcg_gauge_plaquette": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, c_dbl_p]),
     "bcg_basis_dot": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_void_p, c_dbl_p]),
     "bcg_basis_axpy": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, c_dbl_p, ctypes.c_double]),
     "bcg_field_copy_columns": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int]),

@@ -509,6 +509,49 @@ def smear(f, links, dir, kappa, n_iter, work=None):
     return f
 
 
+def _rho_table(rho, ndim, dir=None):
+    """a scalar weight (on all pairs, or on all pairs not involving dir) or an ndim x ndim table -> ndim*ndim doubles"""
+    r = np.asarray(rho, dtype=np.float64)
+    d = -1 if dir is None else int(dir)
+    if not -1 <= d < ndim:
+        raise ValueError(f"dir must be None, -1 or a direction of the lattice, got {dir}")
+    if r.ndim == 0:
+        t = np.full((ndim, ndim), float(r))
+        if d >= 0:
+            t[d, :] = 0.0
+            t[:, d] = 0.0
+    else:
+        if r.size != ndim * ndim:
+            raise ValueError(f"expected one weight, or an {ndim} x {ndim} table")
+        if d >= 0:
+            raise ValueError("dir goes with a scalar rho; a table says itself which pairs it smears")
+        t = r.reshape(ndim, ndim)
+    return np.ascontiguousarray(t, dtype=np.float64)
+
+
+def stout_smear(out, links, rho=0.1, n_steps=1, dir=None, work=None):
+    """out = S^n_steps(links): stout smearing of the gauge links on the device (include/blockcg_hip.h,
+    bcg_gauge_stout_smear).  out: a gauge_field; links: a dirac_op or a gauge_field (not written).  rho: one weight, or an
+    ndim x ndim table rho[mu][nu] (diagonal ignored, a zero entry is not evaluated); a scalar rho with dir = t means rho on all
+    pairs not involving t (dir = 3 on a 4-D lattice: spatial smearing, direction 3 copied bit for bit); dir None or -1: all
+    pairs.  work: a gauge_field the steps alternate with (None: allocated for the call when n_steps >= 2); overwritten.
+    Returns out."""
+    ctx = links.ctx
+    t = _rho_table(rho, ctx.ndim, dir)
+    ctx.check(ctx.lib.bcg_gauge_stout_smear(ctx.h, out.h, links.h, _dp(t), int(n_steps), None if work is None else work.h))
+    return out
+
+
+def plaquette(links):
+    """P[mu, nu] = P[nu, mu] = sum_x Re tr[U_mu(x) U_nu(x+mu) U_mu(x+nu)^dagger U_nu(x)^dagger] / (3 V_global) as an
+    ndim x ndim array (include/blockcg_hip.h, bcg_gauge_plaquette); 0 on the diagonal and for directions of extent 1.  links:
+    a dirac_op or a gauge_field.  Summed over all ranks, the same bits on every call."""
+    ctx = links.ctx
+    out = np.zeros((ctx.ndim, ctx.ndim), dtype=np.float64)
+    ctx.check(ctx.lib.bcg_gauge_plaquette(ctx.h, links.h, _dp(out)))
+    return out
+
+
 def _basis_handles(V):
     V = list(V)
     if not V:

@@ -4,6 +4,7 @@
 //                       pair's planner and launchers (apply_shifted's and the solver's), gauge API
 //   capi_solvers.hip    SBCGrQ (phases A / B / C, grouped and deferred updates), CG, SCG, BCG, BCGrQ, true residuals
 //   capi_force.hip      the fermion force of multi-shift solutions (bcg_force_accumulate), gauge-field download / zero
+//   capi_gauge_smear.hip  stout smearing of the links and the plaquette
 //   capi_sources.hip    noise fields, point / wall sources, the slice-resolved inner product
 //   capi_shift.hip      the covariant nearest-neighbour sum with free coefficients, covariant smearing
 //   capi_basis.hip      products between fields of unequal width (V^dagger b, y <- beta y + V C, V^dagger b by slice), the column copy
@@ -179,6 +180,8 @@ int halo_plan(int ndim, const int* gdims, const int* grid, const int* coords, si
 inline bool can_overlap(const bcg_context* c) {
   return c->distributed && c->have_comm && c->comm.halo_exchange_begin && c->comm.halo_exchange_end;
 }
+// post the face messages of the send buffer for site_bytes bytes per site (blocking unless split; capi_operator.hip)
+int exchange_faces(bcg_context* c, size_t site_bytes, bool split, int x3_lo, int x3_n, int x3b_lo, int x3b_n);
 int halo_field(bcg_context* c, const bcg_field* f, bool split = false);
 // the plan of one stencil launch on this context (after ensure_scratch); HOP_FORM_NONE: no specialised kernel serves it
 bcg::HopLaunchPlan plan_stencil(const bcg_context* c, const bcg::LatticeDev& lat, bcg::HopTuning tune, const bcg::HopRequest& rq);

@@ -60,5 +60,6 @@ class dirac_op {
 };
 
 #include "shift.hpp"  // blockcg::shift_sum, covariant_shift, laplacian, smear (extensions)
+#include "gauge.hpp"  // blockcg::stout_smear, plaquette (extensions)
 
 #endif

@@ -371,7 +371,7 @@ int bcg_field_slice_gram(const bcg_field* a, const bcg_field* b, int dir, int n_
  *    out; c0 == 0 does not read in(x).
  *  - A direction of extent 1 has the site itself as both neighbours (as in bcg_dirac_hop).
  *  - With c0 = 0, fwd = 1/2, bwd = -1/2, eta = 1 the call is bcg_dirac_hop to rounding (not bit for bit).
- *  - g: an operator's links or any link-shaped bcg_gauge of the context (e.g. smeared links uploaded with bcg_gauge_upload);
+ *  - g: an operator's links or any link-shaped bcg_gauge of the context (e.g. links smeared on the device by bcg_gauge_stout_smear);
  *    a stale gauge ghost is refreshed first, as by bcg_dirac_hop.
  *  - Full fields: out and in distinct full fields of one width and context.  Half fields: in of parity p, out of parity
  *    1 - p, c0 exactly 0; even extents and half ghost faces as for bcg_dirac_hop_half.
@@ -399,6 +399,47 @@ int bcg_dirac_shift_sum(bcg_context* ctx, const bcg_gauge* g, bcg_field* out, co
  * exchange part-way through the steps leaves the contents of f (and of work) undefined. */
 int bcg_covariant_smear(bcg_context* ctx, const bcg_gauge* g, bcg_field* f, bcg_field* work, int dir, double kappa,
                         int n_iter);
+
+/* ---- gauge links: stout smearing and plaquettes (extensions) ---------------------------------------
+ * Sites are periodic and links general complex 3 x 3, layout [site][mu < ndim][3x3 column-major], as everywhere here.
+ * rho is an ndim x ndim table of real weights, row-major, rho[mu*ndim + nu]; its diagonal is ignored and rho[mu][nu] need
+ * not equal rho[nu][mu].  A direction of GLOBAL extent 1 takes no part, neither as mu nor as nu (unlike
+ * bcg_dirac_shift_sum: a staple through a direction of extent 1 is not a staple).  One step U -> U' is
+ *   C_mu(x)  = sum_{nu != mu} rho[mu][nu] * [ U_nu(x) U_mu(x+nu) U_nu(x+mu)^dagger
+ *                                           + U_nu(x-nu)^dagger U_mu(x-nu) U_nu(x-nu+mu) ]
+ *   Omega    = C_mu(x) U_mu(x)^dagger
+ *   Q        = (i/2) (Omega^dagger - Omega) - (i/6) tr(Omega^dagger - Omega) * 1      (Hermitian, traceless for ANY U)
+ *   U'_mu(x) = exp(iQ) U_mu(x)
+ *  - A term whose rho[mu][nu] is exactly 0 is not evaluated and its links are not read (the zero-coefficient convention of
+ *    bcg_dirac_shift_sum), so non-finite data in links that no term names never reaches out.
+ *  - A direction mu whose whole row of rho is 0 (after the rules above), or whose extent is 1, is copied bit for bit.
+ *  - exp(iQ) = f0 + f1 Q + f2 Q^2 in the Cayley-Hamilton form of Morningstar and Peardon, exact to rounding for every
+ *    Hermitian traceless Q, Q = 0 and Q with two equal eigenvalues included (DESIGN.md section 8m lists the guards).
+ *
+ * bcg_gauge_stout_smear: out = S^n_steps(in).  in is not written and may be an operator's links.  The steps alternate between
+ * out and work so that the last one writes out, with no final copy; n_steps = 0 (or a table without a single live term) is a
+ * device copy of in to out.  work: a container of the context, contents undefined afterwards; NULL: allocated for the call
+ * when n_steps >= 2.  The result does not depend on whether work was passed: the same bits.  out's gauge ghost is marked
+ * stale.  Divided lattices: two blocking exchanges per step (the faces of all ndim links, then the backward staples
+ * U_nu^dagger U_mu U_nu(+mu) of the high faces, so no corner message is needed); every rank makes the same call, the checks
+ * use global data only, and memory is allocated (and agreed on) before the first launch or exchange.
+ *  - BCG_ERR_INVALID: a NULL ctx, out, in or rho; out == in, work == out or work == in; a container of another context;
+ *    n_steps < 0; a non-finite entry of rho off the diagonal.  BCG_ERR_COMM: a divided lattice without a bcg_comm.
+ *    BCG_ERR_UNSUPPORTED: V_local * ndim >= 2^31.  A call that fails these checks leaves out as it was.
+ *  - Profile key "stout_smear", one entry per step: 2 * 144 ndim bytes per site (every link read once and written once);
+ *    flops 936 per evaluated (mu, nu) term and site (four 3 x 3 products, two scaled sums) plus 798 per smeared link (Omega,
+ *    Q^2, the final product, the coefficients and the polynomial).
+ *
+ * bcg_gauge_plaquette: for mu < nu, both of extent > 1,
+ *   out[mu*ndim + nu] = out[nu*ndim + mu] = (1 / (3 V_global)) sum_x Re tr[ U_mu(x) U_nu(x+mu) U_mu(x+nu)^dagger U_nu(x)^dagger ]
+ * and every other entry of out is 0.  Summed over all ranks with one bcg_comm.allreduce_sum and identical on every rank; the
+ * same bits on every call (fixed blocks, block sums added in a fixed order, no atomics, as bcg_field_slice_dot).  Refreshes
+ * nothing and writes nothing to g (a divided lattice exchanges the link faces into a buffer of the call).  Synchronizes the
+ * stream.  BCG_ERR_INVALID: a NULL argument or links of another context; BCG_ERR_COMM: a divided lattice without a bcg_comm.
+ *  - Profile key "plaquette": 144 ndim bytes per site, 468 flops per plane and site. */
+int bcg_gauge_stout_smear(bcg_context* ctx, bcg_gauge* out, const bcg_gauge* in, const double* rho /* ndim*ndim */,
+                          int n_steps, bcg_gauge* work /* NULL: allocated for the call when n_steps >= 2 */);
+int bcg_gauge_plaquette(bcg_context* ctx, const bcg_gauge* g, double* out /* ndim*ndim */);
 
 /* ---- products with a basis of another width (extensions) ----------------------------------------
  * V is a list of nv >= 1 fields of one context, of any widths 1 .. 32, with the parity and site count of b / y.  K is the
